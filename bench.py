@@ -2,7 +2,7 @@
 """Headline benchmark: poses/sec of one "pose unit" = LC-loss forward+backward + one weighted-PnP solve,
 B=256 poses x N=64 correspondences per GPU (BASELINE.json metric, configs[1]), fp32 I/O, synthetic inputs resident in HBM.
 
-    python bench.py --gpus N --steps 200 --warmup 20
+    python bench.py --gpus N --steps 200 --warmup 20 [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a fresh `python -m torch.distributed.run`
 child, before this process has touched the GPU) and relays the child's line and return code; launched by torchrun (WORLD_SIZE
@@ -11,10 +11,13 @@ set) it is one of the ranks, and a WORLD_SIZE that differs from --gpus is an err
 One process per GPU; the batch is sharded by pose (every pose is independent: SURVEY.md 8e), so there is no data-path
 collective -- only the timing barrier.  Scaling is weak: each rank runs its own B=256 batch.
 A step = ONE launch of the fused kernel (lc_pose_unit2_f32: the loss workgroups -- loss + d/d pts2d, d/d inv_std, d/d pts3d for
-the `.mean()` cotangent -- and the LM-solve workgroups share a grid).  Two launch forms are timed with the same protocol and both
-ride at the top level of the line: `value` (the K steps of a region are K kernel nodes of one hipGraph launch) and
-`value_stream_order` (the same K launches issued one by one from Python).  Rank 0 prints ONE JSON line; it also carries the
-dense configs' hot-path shapes (`dense`: glmo B=32 N=1024, zlmo B=32 N=1849), the keypoint head and the CPU baseline.
+the `.mean()` cotangent -- and the LM-solve workgroups share a grid), issued as a kernel node of a hipGraph (graphs of at most
+GRAPH_CHUNK nodes, replayed back to back).  A plain run sets up, warms up with exactly --warmup steps, times exactly --steps steps
+(one region, barrier + synchronize on both sides; `--regions R` times R such regions and reports the median), writes the last
+step's outputs if --dump-outputs is given, and prints ONE JSON line (rank 0).  `--full` adds everything else the line used to carry:
+the stream-order form of the same launches (`value_stream_order`), the strong split of an N-rank run, the per-kernel times and
+roofline, the large-batch steady state, the dense configs' hot-path shapes (`dense`: glmo B=32 N=1024, zlmo B=32 N=1849), the
+test-time chains, the keypoint head and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -43,6 +46,10 @@ SIMD_CYCLES_PER_S = 1024 * 2.4e9  # 256 CUs x 4 SIMDs x 2.4 GHz (MI355X_MICROARC
 # the dense configs' per-GPU hot-path shapes (BASELINE.json configs[2]-[4]): reference configs/glmo.yaml (B=32, 64x64 output,
 # dense_sample 2 -> N = 32*32), zlmo (128x128 output, dense_sample 3 -> N = 43*43); losses.py:336-386, test.py:67-136
 DENSE_WORKLOADS = {"glmo_dense": (32, 1024), "zlmo_dense": (32, 1849)}
+# kernel nodes per captured hipGraph of the timed steps: --steps of any size replays graphs of at most this many nodes back to back
+# (capturing and instantiating one node per step would make the set-up grow with --steps)
+GRAPH_CHUNK = 1000
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much (a fixed, seeded sample of the poses beyond it)
 
 
 def algorithmic_bytes(N: int, want_pts3d: bool):
@@ -171,29 +178,52 @@ def cpu_baseline(B, N, seed, budget_s=18.0):
                        f"fwd+bwd + C/OpenMP LM, {cores} threads = the best SUSTAINED rate of {counts}; every count ran the same loop)")
 
 
+def dump_outputs(out_dir: str, arrays: dict, limit_bytes: int = DUMP_LIMIT_BYTES):
+    """--dump-outputs: `arrays` (per-pose tensors, dim 0 = pose) as out_dir/<name>.npy in float32 (the solve's int32 return codes
+    too: small integers are exact).  Above limit_bytes in all, the same fixed, seeded sample of poses from every array (its pose
+    indices in out_dir/sample_rows.npy, float64)."""
+    import numpy as np
+
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    B = len(next(iter(host.values())))
+    per_pose = sum(a.nbytes for a in host.values()) // B
+    keep = max(1, min(B, (limit_bytes - 4096) // (per_pose + 8)))  # (4096: the .npy headers)
+    os.makedirs(out_dir, exist_ok=True)
+    if keep < B:
+        rows = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+        host = {k: a[rows] for k, a in host.items()}
+        np.save(os.path.join(out_dir, "sample_rows.npy"), rows.astype(np.float64))
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--regions", type=int, default=51, help="timed regions of exactly --steps steps each (barrier + synchronize on both "
-                    "sides of every region); the MEDIAN region is reported (one 3 ms region moves +-8 %% with launch jitter)")
-    ap.add_argument("--steady-batch", type=int, default=65536, help="B of the in-run steady-state measurement (0: skip)")
+    ap.add_argument("--regions", type=int, default=1, help="timed regions of exactly --steps steps each (barrier + synchronize on both "
+                    "sides of every region); the MEDIAN region is reported.  Default 1: --steps is the number of timed steps")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: stream-order form, strong split, "
+                    "per-kernel times and roofline, steady state, dense shapes, test-time chains, keypoint head, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed "
+                    "(rank 0's batch) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
+    ap.add_argument("--steady-batch", type=int, default=65536, help="--full: B of the in-run steady-state measurement (0: skip)")
     ap.add_argument("--batch", type=int, default=256, help="poses per GPU per step")
     ap.add_argument("--npts", type=int, default=64)
     ap.add_argument("--slots", type=int, default=4, help="--launch streams: independent batches in flight (own buffers, own stream)")
     ap.add_argument("--launch", default="graph_region", choices=["fused", "eager", "eager2", "graph", "graph2", "graph_fused", "graph_region", "streams"],
                     help="graph_region (default): a step is ONE fused launch (lc_pose_unit2_f32: loss and PnP workgroups share a grid) and "
-                         "the K steps of a timed region are K kernel nodes of one hipGraph launch -- `value`; the stream-order form of the "
-                         "same launches is timed too -- `value_stream_order`; fused: only the stream-order form; eager: two launches per "
+                         "the K steps of a timed region are K kernel nodes of hipGraph launches (at most GRAPH_CHUNK nodes each) -- `value`; "
+                         "--full times the stream-order form of the same launches too -- `value_stream_order`; fused: only the stream-order form; eager: two launches per "
                          "step on one stream; eager2: LM solve forked onto a second stream; graph / graph2 / graph_fused: one step replayed "
                          "as a hipGraph")
     ap.add_argument("--workload", default="all", choices=["all", "metric", *DENSE_WORKLOADS],
-                    help="which extra blocks ride on the line next to the headline (which is always the metric's B=256 N=64): the dense "
+                    help="--full: which extra blocks ride on the line next to the headline (which is always the metric's B=256 N=64): the dense "
                          "configs' hot-path shapes `dense.glmo_dense` (B=32 N=1024) and `dense.zlmo_dense` (B=32 N=1849); metric: none")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-head", action="store_true", help="skip the keypoint-head measurement attached as out['head']")
-    ap.add_argument("--cpu-budget", type=float, default=18.0, help="seconds of sustained CPU-baseline loops, split evenly over the thread counts of the sweep")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-head", action="store_true", help="--full: skip the keypoint-head measurement attached as out['head']")
+    ap.add_argument("--cpu-budget", type=float, default=18.0, help="--full: seconds of sustained CPU-baseline loops, split evenly over the thread counts of the sweep")
     return ap.parse_args(argv)
 
 
@@ -265,6 +295,8 @@ def main():
     share_gpu = os.environ.get("LC_BENCH_SHARE_GPU", "0") == "1"
     # torch.cuda.device_count() does not initialise the GPU on this image; nothing else may touch it before a self-launch
     kind, val = launch_plan(args.gpus, os.environ.get("WORLD_SIZE"), torch.cuda.device_count(), share_gpu)
+    if args.steps < 1 or args.warmup < 0:
+        kind, val = "error", f"--steps {args.steps} --warmup {args.warmup}: need at least one timed step and no negative warm-up"
     if kind == "error":
         print(f"bench.py: {val}", file=sys.stderr)
         raise SystemExit(2)
@@ -362,6 +394,11 @@ def main():
         def check(self):
             assert int(self.ret.sum().item()) == 0 and bool(torch.isfinite(self.loss).all())
 
+        def outputs(self):
+            """What a caller of the pose unit receives (lc_pose_unit2_f32's output buffers), by name."""
+            return {"loss": self.loss, "d_pts2d": self.d_u, "d_inv_std": self.d_s, "d_pts3d": self.d_x,
+                    "pnp_states": self.states, "pnp_result_tr": self.tr, "pnp_rets": self.ret}
+
         def mean_lm_iterations(self):
             """Trust-region iterations per pose of this batch (the stand-alone solve is bit-identical to the fused grid's half:
             tests/test_gpu_fused.py), for SURVEY 8(d)'s flop figure."""
@@ -432,9 +469,20 @@ def main():
             torch.cuda.synchronize(dev)
             return None
 
+    def capture_steps(fn, n):
+        """`n` calls of fn as kernel nodes of hipGraphs: (body, chunk, tail) = a graph of chunk = min(n, GRAPH_CHUNK) calls, replayed
+        n // chunk times, and a graph of the n % chunk calls left over (None if there are none); None (with the reason on stderr) if
+        the runtime cannot capture them."""
+        chunk = min(n, GRAPH_CHUNK)
+        body = capture(fn, chunk)
+        tail = capture(fn, n % chunk) if (body is not None and n % chunk) else None
+        if body is None or (n % chunk and tail is None):
+            return None
+        return body, chunk, tail
+
     graph = None
     if args.launch.startswith("graph"):
-        graph = capture(step_eager, args.steps if args.launch == "graph_region" else 1)
+        graph = capture_steps(step_eager, args.steps if args.launch == "graph_region" else 1)
         # every rank times the SAME launch form: if one rank could not capture, all of them issue the launches one by one
         if not all_agree(graph is not None):
             if args.launch != "graph_region":
@@ -448,52 +496,77 @@ def main():
 
     from lc_amd import dist as lcd
 
-    def timed_regions(step, steps_per_call):
-        """The protocol: W warm-up steps, then R regions of exactly K steps, each bracketed by barrier + synchronize; a region
+    def stepper(fn, g):
+        """(run, warm): run() issues exactly --steps calls of fn, warm() exactly --warmup (at least one).  With g = capture_steps(fn, ...)
+        the whole chunks are replays of its body graph; the timed steps' remainder is its tail graph, the warm-up's remainder fn itself."""
+        def run():
+            if g is None:
+                for _ in range(args.steps):
+                    fn()
+                return
+            body, chunk, tail = g
+            for _ in range(args.steps // chunk):
+                body.replay()
+            if tail is not None:
+                tail.replay()
+
+        def warm():
+            n = max(1, args.warmup)
+            if g is not None:
+                for _ in range(n // g[1]):
+                    g[0].replay()
+                n %= g[1]
+            for _ in range(n):
+                fn()
+        return run, warm
+
+    def timed_regions(run, warm):
+        """The protocol: W warm-up steps, then R regions (default 1) of exactly K steps, each bracketed by barrier + synchronize; a region
         lasts as long as its slowest rank (MAX over ranks), the MEDIAN region is reported."""
-        for _ in range(max(1, args.warmup // steps_per_call)):
-            step()
+        warm()
         region_s = []
         for _ in range(max(1, args.regions)):
             fence()  # synchronize + barrier + synchronize: every rank starts the region together
             t0 = time.perf_counter()
-            for _ in range(args.steps // steps_per_call):
-                step()
+            run()
             torch.cuda.synchronize(dev)  # this rank's K steps are done ...
             region_s.append(time.perf_counter() - t0)
             barrier()  # ... and the region ends when the slowest rank is (MAX over ranks below); the collective's own
             # latency (tens of us over RCCL) is not part of the K steps
         return lcd.aggregate_regions(region_s, args.steps, device="cpu")  # per-rank region times travel over gloo
 
-    if graph is not None:
-        agg = timed_regions(graph.replay, args.steps if args.launch == "graph_region" else 1)
-    else:
-        agg = timed_regions(step_eager, 1)
-    # the stream-order form of the same K launches, same protocol (what a caller pays who issues the launches one by one)
-    agg_so = timed_regions(step_fused, 1) if args.launch == "graph_region" else (agg if args.launch == "fused" else None)
+    agg = timed_regions(*stepper(step_eager, graph))
     elapsed = agg["median_region_s"]
-    # SURVEY.md 8(e) writes the partition as "32/GPU at B=256, 8 GPUs": beside the weak headline (B poses per rank) the STRONG split of ONE
-    # global batch of B poses over the ranks (lc_amd.dist.shard_range), same launch form, same region protocol.  A 13 us launch is bound by
-    # per-wave latency, so the strong line is expected to stay flat -- a fact to print beside the weak curve, not to omit.
-    strong = None
-    if world > 1 and args.launch in ("fused", "graph_region") and B >= world:
-        lo, hi = lcd.shard_range(B, rank, world)
-        s_unit = Unit(B, N, seed=12345, rows=(lo, hi))  # every rank builds the same global batch and keeps its shard
-        s_graph = capture(s_unit.launch_fused, args.steps) if args.launch == "graph_region" else None
-        use_graph = all_agree(s_graph is not None)
-        s_agg = timed_regions(s_graph.replay, args.steps) if use_graph else timed_regions(s_unit.launch_fused, 1)
-        s_unit.check()
-        strong = {"scaling": "strong", "value": B * args.steps / s_agg["median_region_s"], "unit": "poses/s", "global_batch": B,
-                  "per_rank_batch": hi - lo, "ms_per_step": s_agg["ms_per_step"], "ranks_seen": s_agg["ranks_seen"],
-                  "per_rank_ms_per_step": s_agg["per_rank_ms_per_step"], "launch": "graph_region" if use_graph else "fused",
-                  "note": f"one global batch of {B} poses split contiguously over {world} rank(s) (lc_amd.dist.shard_range: {hi - lo} on this rank), no "
-                          "data-path collective; same regions / barrier / MAX-over-ranks / median protocol as the weak headline.  The launch is "
-                          "latency-bound (one wave per pose, the slowest pose's LM iterations): fewer poses per rank do not shorten it"}
     if args.launch == "streams":
         for u, _ in slot_state:
             u.check()
+        last_unit = slot_state[(slot_i[0] - 1) % len(slot_state)][0]
     else:
         main_unit.check()
+        last_unit = main_unit
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_unit.outputs())
+
+    agg_so, strong = None, None
+    if args.full:
+        # the stream-order form of the same K launches, same protocol (what a caller pays who issues the launches one by one)
+        agg_so = timed_regions(*stepper(step_fused, None)) if args.launch == "graph_region" else (agg if args.launch == "fused" else None)
+        # SURVEY.md 8(e) writes the partition as "32/GPU at B=256, 8 GPUs": beside the weak headline (B poses per rank) the STRONG split of ONE
+        # global batch of B poses over the ranks (lc_amd.dist.shard_range), same launch form, same region protocol.  A 13 us launch is bound by
+        # per-wave latency, so the strong line is expected to stay flat -- a fact to print beside the weak curve, not to omit.
+        if world > 1 and args.launch in ("fused", "graph_region") and B >= world:
+            lo, hi = lcd.shard_range(B, rank, world)
+            s_unit = Unit(B, N, seed=12345, rows=(lo, hi))  # every rank builds the same global batch and keeps its shard
+            s_graph = capture_steps(s_unit.launch_fused, args.steps) if args.launch == "graph_region" else None
+            use_graph = all_agree(s_graph is not None)
+            s_agg = timed_regions(*stepper(s_unit.launch_fused, s_graph if use_graph else None))
+            s_unit.check()
+            strong = {"scaling": "strong", "value": B * args.steps / s_agg["median_region_s"], "unit": "poses/s", "global_batch": B,
+                      "per_rank_batch": hi - lo, "ms_per_step": s_agg["ms_per_step"], "ranks_seen": s_agg["ranks_seen"],
+                      "per_rank_ms_per_step": s_agg["per_rank_ms_per_step"], "launch": "graph_region" if use_graph else "fused",
+                      "note": f"one global batch of {B} poses split contiguously over {world} rank(s) (lc_amd.dist.shard_range: {hi - lo} on this rank), no "
+                              "data-path collective; same regions / barrier / MAX-over-ranks / median protocol as the weak headline.  The launch is "
+                              "latency-bound (one wave per pose, the slowest pose's LM iterations): fewer poses per rank do not shorten it"}
 
     # per-kernel launch duration with events on the launch stream (torch's current stream == the kernels' stream)
     def kernel_ms(fn, reps=200, windows=5):
@@ -678,56 +751,6 @@ def main():
                 "max_rotation_error": float((Re - Rg).abs().max())}
 
     if rank == 0:
-        t_loss = kernel_ms(main_unit.launch_loss)
-        t_pnp = kernel_ms(main_unit.launch_pnp)
-        by_loss, by_pnp = algorithmic_bytes(N, True)
-        dom = ("lc_cov_loss_kernel", t_loss, by_loss) if t_loss >= t_pnp else ("lc_pnp_lm_kernel", t_pnp, by_pnp)
-        kernel_us = {"lc_cov_loss_kernel": t_loss * 1e3, "lc_pnp_lm_kernel": t_pnp * 1e3}
-        fused_forms = args.launch in ("fused", "graph_fused", "graph_region")
-        if fused_forms:
-            t_unit = kernel_ms(step_fused)  # launches issued one by one (stream order)
-            kernel_us["lc_pose_unit_kernel"] = t_unit * 1e3
-            if args.launch == "graph_region":  # the pattern of the timed region: the kernel as a node of the K-step graph (events around replays)
-                kernel_us["lc_pose_unit_kernel_stream_order"] = t_unit * 1e3
-                t_unit = kernel_ms(graph.replay, reps=max(1, 200 // args.steps)) / args.steps
-                kernel_us["lc_pose_unit_kernel"] = t_unit * 1e3
-            dom = ("lc_pose_unit_kernel", t_unit, by_loss + by_pnp)
-            kernel_us["lc_pose_unit_kernel_p10_p50_p90"] = kernel_percentiles_us(step_fused)
-        # every figure of the roofline block is formed from the PROTOCOL's step (ms_per_step of this rank's line), not from the
-        # event-timed replay; the event-timed launch durations ride along in kernel_us
-        step_s = elapsed / args.steps if fused_forms else dom[1] * 1e-3
-        hbm_gbs = dom[2] * B / step_s / 1e9
-        poses_per_s = B / step_s
-        it_mean, it_max = main_unit.mean_lm_iterations()
-        fl_loss, fl_pnp = algorithmic_flops(N, it_mean + 1.0)
-        tflops = (fl_loss + fl_pnp) * B / step_s / 1e12
-        fl_nom = 350e3 * N / 64.0  # SURVEY.md 8(d)'s nominal pose unit: 115 + 23 x ~10 kflop = ~350 kflop, whatever the batch executes
-        flops = {"bound": "fp64_vector", "achieved": tflops, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
-                 "frac": tflops / FP64_VECTOR_PEAK_TFLOPS,
-                 "nominal_frac": fl_nom * B / step_s / 1e12 / FP64_VECTOR_PEAK_TFLOPS,
-                 "nominal_note": "`frac` counts the LM iterations this batch executes; `nominal_frac` credits SURVEY.md 8(d)'s nominal ~350 kflop "
-                                 "pose unit (~10 iterations) on the same step time -- the two figures people quote, both from this line",
-                 "algorithmic_kflop_per_pose": {"loss": fl_loss / 1e3, "pnp": fl_pnp / 1e3},
-                 "lm_iterations": {"mean": it_mean, "max": it_max},
-                 "note": "SURVEY.md 8(d): 115 kflop (loss fwd+bwd) + 23 kflop x (LM iterations + 1 initial evaluation) per pose, the "
-                         "iteration count read from the solve's `iters` output on this batch; peak = fp64 vector (the LM runs in fp64)"}
-        ctr, src = static_counters(dom[0], B, N)
-        hbm = {"bound": "hbm", "achieved": hbm_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_gbs / HBM_PEAK_GBS,
-               "algorithmic_bytes_per_pose": {"loss": by_loss, "pnp": by_pnp},
-               "note": "secondary: 5 KB working set per pose, one wave per pose -- HBM never binds this kernel"}
-        # Top level = SURVEY.md 8(d)'s figure: algorithmic flops (measured LM iterations) against the fp64 vector peak.  The kernel's own
-        # VALU-issue ratio rides along as `valu_issue` -- its peak is derived from the kernel's instruction count, so it can show latency
-        # hiding but never a wasted instruction (VERDICT r4 #4a).
-        roof = dict(flops, kernel=dom[0], traffic=ctr.get("bytes_per_launch") if ctr is not None else None, kernel_us=kernel_us, hbm=hbm)
-        if ctr is not None:
-            roof["counters_from"] = src
-        if ctr is not None and ctr.get("sq", {}).get("SQ_ACTIVE_INST_VALU"):
-            cyc, peak = valu_bound(ctr["sq"], B)
-            roof["valu_issue"] = {"bound": "valu_issue", "achieved": poses_per_s, "peak": peak, "unit": "poses/s", "frac": poses_per_s / peak,
-                                  "valu_insts_per_pose": ctr["sq"]["SQ_INSTS_VALU"] / B, "simd_cycles_per_pose": cyc,
-                                  "note": "how much of the kernel's OWN VALU issue time the launch hides: peak = 1024 SIMDs x 2.4 GHz / VALU-issue "
-                                          "SIMD-cycles per pose (SQ_ACTIVE_INST_VALU of the committed counter pass).  Self-derived -- a latency-hiding "
-                                          "ratio, not a roofline: it cannot show a wasted instruction"}
         out = {
             "metric": METRIC,
             "value": B * world * args.steps / elapsed,
@@ -748,50 +771,103 @@ def main():
                        **({"slots_in_flight": args.slots} if args.launch == "streams" else {})},
             "timing": {"protocol": f"{agg['regions']} regions of exactly {args.steps} steps, barrier + synchronize around each, MAX over ranks "
                                    f"per region, MEDIAN region reported"
-                                   + ("; the K steps of a region are K kernel nodes of one hipGraph launch" if args.launch == "graph_region" else ""),
+                                   + (f"; the K steps of a region are K kernel nodes of hipGraph launches (graphs of at most {GRAPH_CHUNK} nodes, "
+                                      "replayed back to back)" if args.launch == "graph_region" else ""),
                        "region_ms_per_step": agg["region_ms_per_step"]},
             "ranks_seen": agg["ranks_seen"], "collective_backend": coll["backend"] if coll else "none",
             "region_times_gathered_over": agg["backend"],
             "rccl_version": rccl_version() if (coll and coll["backend"] == "nccl") else None,
             "per_rank_ms_per_step": agg["per_rank_ms_per_step"],
-            "roofline": roof,
             "library": {"embedded_source_hash": lib.lc_amd_source_hash().decode(), "source_hash_on_disk": __import__("lc_amd.build", fromlist=["x"]).source_hash()},
         }
         if coll and coll["rccl_error"]:
             out["rccl_error"] = coll["rccl_error"]
-        if strong is not None:
-            out["strong"] = strong
-        if agg_so is not None:
-            out["value_stream_order"] = B * world * args.steps / agg_so["median_region_s"]
-            out["ms_per_step_stream_order"] = agg_so["ms_per_step"]
-            out["timing"]["stream_order"] = {"what": "the same K fused launches per region issued one by one from Python (per-launch host "
-                                                     "cost included), same regions / barrier / MAX-over-ranks / median protocol",
-                                             "region_ms_per_step": agg_so["region_ms_per_step"],
-                                             "per_rank_ms_per_step": agg_so["per_rank_ms_per_step"]}
-        if args.steady_batch > 0 and world == 1 and args.launch in ("fused", "graph_region"):
-            Bs, pps, ms = steady_state(args.steady_batch)
-            ss = {"B": Bs, "poses_per_s": pps, "ms_per_launch": ms}
-            if "valu_issue" in roof:
-                ss["valu_frac"] = pps / roof["valu_issue"]["peak"]
-            fl_l, fl_p = algorithmic_flops(N, it_mean + 1.0)
-            ss["flops_frac"] = (fl_l + fl_p) * pps / 1e12 / FP64_VECTOR_PEAK_TFLOPS
-            out["steady_state"] = ss
-        if world == 1 and args.workload != "metric":
-            out["dense"] = {k: dense_block(k, *v) for k, v in DENSE_WORKLOADS.items() if args.workload in ("all", k)}
-        if world == 1 and args.workload == "all":
-            out["test_time"] = {}
-            for tt in ("zlmo", "zlmo_bf16", "glmo", "gsplmo", "hybrid_r03"):
-                try:  # auxiliary blocks: whatever happens in one, the headline above is printed
-                    out["test_time"][tt] = test_time_block(tt)
-                except Exception as e:  # noqa: BLE001
-                    out["test_time"][tt] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if world == 1 and not args.no_head:
-            # the third kernel family of the path (keypoint head), HBM-bound; its own line: bench_head.py
-            from bench_head import measure_head
-            h = measure_head(dev, steps=10, warmup=2)
-            out["head"] = {"metric": h["metric"], "value": h["value"], "unit": h["unit"], "config": h["config"], "roofline": h["roofline"]}
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(B, N, seed=rank, budget_s=args.cpu_budget)
+        if args.full:
+            t_loss = kernel_ms(main_unit.launch_loss)
+            t_pnp = kernel_ms(main_unit.launch_pnp)
+            by_loss, by_pnp = algorithmic_bytes(N, True)
+            dom = ("lc_cov_loss_kernel", t_loss, by_loss) if t_loss >= t_pnp else ("lc_pnp_lm_kernel", t_pnp, by_pnp)
+            kernel_us = {"lc_cov_loss_kernel": t_loss * 1e3, "lc_pnp_lm_kernel": t_pnp * 1e3}
+            fused_forms = args.launch in ("fused", "graph_fused", "graph_region")
+            if fused_forms:
+                t_unit = kernel_ms(step_fused)  # launches issued one by one (stream order)
+                kernel_us["lc_pose_unit_kernel"] = t_unit * 1e3
+                if args.launch == "graph_region":  # the pattern of the timed region: the kernel as a node of the timed graphs (events around replays)
+                    kernel_us["lc_pose_unit_kernel_stream_order"] = t_unit * 1e3
+                    body, chunk, _ = graph
+                    t_unit = kernel_ms(body.replay, reps=max(1, 200 // chunk)) / chunk
+                    kernel_us["lc_pose_unit_kernel"] = t_unit * 1e3
+                dom = ("lc_pose_unit_kernel", t_unit, by_loss + by_pnp)
+                kernel_us["lc_pose_unit_kernel_p10_p50_p90"] = kernel_percentiles_us(step_fused)
+            # every figure of the roofline block is formed from the PROTOCOL's step (ms_per_step of this rank's line), not from the
+            # event-timed replay; the event-timed launch durations ride along in kernel_us
+            step_s = elapsed / args.steps if fused_forms else dom[1] * 1e-3
+            hbm_gbs = dom[2] * B / step_s / 1e9
+            poses_per_s = B / step_s
+            it_mean, it_max = main_unit.mean_lm_iterations()
+            fl_loss, fl_pnp = algorithmic_flops(N, it_mean + 1.0)
+            tflops = (fl_loss + fl_pnp) * B / step_s / 1e12
+            fl_nom = 350e3 * N / 64.0  # SURVEY.md 8(d)'s nominal pose unit: 115 + 23 x ~10 kflop = ~350 kflop, whatever the batch executes
+            flops = {"bound": "fp64_vector", "achieved": tflops, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
+                     "frac": tflops / FP64_VECTOR_PEAK_TFLOPS,
+                     "nominal_frac": fl_nom * B / step_s / 1e12 / FP64_VECTOR_PEAK_TFLOPS,
+                     "nominal_note": "`frac` counts the LM iterations this batch executes; `nominal_frac` credits SURVEY.md 8(d)'s nominal ~350 kflop "
+                                     "pose unit (~10 iterations) on the same step time -- the two figures people quote, both from this line",
+                     "algorithmic_kflop_per_pose": {"loss": fl_loss / 1e3, "pnp": fl_pnp / 1e3},
+                     "lm_iterations": {"mean": it_mean, "max": it_max},
+                     "note": "SURVEY.md 8(d): 115 kflop (loss fwd+bwd) + 23 kflop x (LM iterations + 1 initial evaluation) per pose, the "
+                             "iteration count read from the solve's `iters` output on this batch; peak = fp64 vector (the LM runs in fp64)"}
+            ctr, src = static_counters(dom[0], B, N)
+            hbm = {"bound": "hbm", "achieved": hbm_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_gbs / HBM_PEAK_GBS,
+                   "algorithmic_bytes_per_pose": {"loss": by_loss, "pnp": by_pnp},
+                   "note": "secondary: 5 KB working set per pose, one wave per pose -- HBM never binds this kernel"}
+            # Top level = SURVEY.md 8(d)'s figure: algorithmic flops (measured LM iterations) against the fp64 vector peak.  The kernel's own
+            # VALU-issue ratio rides along as `valu_issue` -- its peak is derived from the kernel's instruction count, so it can show latency
+            # hiding but never a wasted instruction (VERDICT r4 #4a).
+            roof = dict(flops, kernel=dom[0], traffic=ctr.get("bytes_per_launch") if ctr is not None else None, kernel_us=kernel_us, hbm=hbm)
+            if ctr is not None:
+                roof["counters_from"] = src
+            if ctr is not None and ctr.get("sq", {}).get("SQ_ACTIVE_INST_VALU"):
+                cyc, peak = valu_bound(ctr["sq"], B)
+                roof["valu_issue"] = {"bound": "valu_issue", "achieved": poses_per_s, "peak": peak, "unit": "poses/s", "frac": poses_per_s / peak,
+                                      "valu_insts_per_pose": ctr["sq"]["SQ_INSTS_VALU"] / B, "simd_cycles_per_pose": cyc,
+                                      "note": "how much of the kernel's OWN VALU issue time the launch hides: peak = 1024 SIMDs x 2.4 GHz / VALU-issue "
+                                              "SIMD-cycles per pose (SQ_ACTIVE_INST_VALU of the committed counter pass).  Self-derived -- a latency-hiding "
+                                              "ratio, not a roofline: it cannot show a wasted instruction"}
+            out["roofline"] = roof
+            if strong is not None:
+                out["strong"] = strong
+            if agg_so is not None:
+                out["value_stream_order"] = B * world * args.steps / agg_so["median_region_s"]
+                out["ms_per_step_stream_order"] = agg_so["ms_per_step"]
+                out["timing"]["stream_order"] = {"what": "the same K fused launches per region issued one by one from Python (per-launch host "
+                                                         "cost included), same regions / barrier / MAX-over-ranks / median protocol",
+                                                 "region_ms_per_step": agg_so["region_ms_per_step"],
+                                                 "per_rank_ms_per_step": agg_so["per_rank_ms_per_step"]}
+            if args.steady_batch > 0 and world == 1 and args.launch in ("fused", "graph_region"):
+                Bs, pps, ms = steady_state(args.steady_batch)
+                ss = {"B": Bs, "poses_per_s": pps, "ms_per_launch": ms}
+                if "valu_issue" in roof:
+                    ss["valu_frac"] = pps / roof["valu_issue"]["peak"]
+                fl_l, fl_p = algorithmic_flops(N, it_mean + 1.0)
+                ss["flops_frac"] = (fl_l + fl_p) * pps / 1e12 / FP64_VECTOR_PEAK_TFLOPS
+                out["steady_state"] = ss
+            if world == 1 and args.workload != "metric":
+                out["dense"] = {k: dense_block(k, *v) for k, v in DENSE_WORKLOADS.items() if args.workload in ("all", k)}
+            if world == 1 and args.workload == "all":
+                out["test_time"] = {}
+                for tt in ("zlmo", "zlmo_bf16", "glmo", "gsplmo", "hybrid_r03"):
+                    try:  # auxiliary blocks: whatever happens in one, the headline above is printed
+                        out["test_time"][tt] = test_time_block(tt)
+                    except Exception as e:  # noqa: BLE001
+                        out["test_time"][tt] = {"error": f"{type(e).__name__}: {e}"[:300]}
+            if world == 1 and not args.no_head:
+                # the third kernel family of the path (keypoint head), HBM-bound; its own line: bench_head.py
+                from bench_head import measure_head
+                h = measure_head(dev, steps=10, warmup=2)
+                out["head"] = {"metric": h["metric"], "value": h["value"], "unit": h["unit"], "config": h["config"], "roofline": h["roofline"]}
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(B, N, seed=rank, budget_s=args.cpu_budget)
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out/icache_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 -L 2>/dev/null | grep -i -E "SQC_ICACHE|SQ_IFETCH|SQ_INST_CYCLES_VMEM|SQC_INST|ICACHE|IFETCH|SQ_WAIT_INST|SQ_INST_LEVEL" | sort -u | head -60 > "$OUT/counters_listed.txt" 2>&1
-BENCH="python3 $ROOT/bench.py --steps 100 --warmup 10 --regions 3 --steady-batch 0 --no-cpu-baseline --no-head"
+BENCH="python3 $ROOT/bench.py --full --steps 100 --warmup 10 --regions 3 --steady-batch 0 --no-cpu-baseline --no-head"
 export CFG=glmo
 TT="python3 $ROOT/scripts/ubench/config_test_time.py"
 i=0

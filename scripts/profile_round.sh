@@ -12,7 +12,7 @@ SHA=${2:-unknown}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --steps 300 --warmup 30 --regions 3 --steady-batch 0 --no-cpu-baseline --no-head"
+BENCH="python3 $ROOT/bench.py --full --steps 300 --warmup 30 --regions 3 --steady-batch 0 --no-cpu-baseline --no-head"
 HEAD="python3 $ROOT/bench_head.py --steps 20 --warmup 3"
 SWEEP="python3 $ROOT/scripts/ubench/sweep_pose_unit.py"
 SQ="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_LDS"

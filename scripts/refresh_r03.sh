@@ -8,8 +8,8 @@ cd "${GRAFT_REPO_ROOT:-$(pwd)}"
 SHA=${1:-unknown}
 bash scripts/profile_round.sh r03 "$SHA" > gpurun_out/profile_round.log 2>&1 < /dev/null
 O=gpurun_out/prof_r03
-timeout 600 python3 bench.py 2>/dev/null < /dev/null | tail -1 > $O/bench_default.json
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null < /dev/null | tail -1 > $O/bench_k20.json
+timeout 600 python3 bench.py --full 2>/dev/null < /dev/null | tail -1 > $O/bench_default.json
+timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 2>/dev/null < /dev/null | tail -1 > $O/bench_k20.json
 timeout 300 python3 bench_head.py 2>/dev/null < /dev/null | tail -1 > $O/bench_head_f32.json
 timeout 300 python3 bench_head.py --dtype bf16 2>/dev/null < /dev/null | tail -1 > $O/bench_head_bf16.json
 timeout 300 python3 bench_head.py --dtype f16 2>/dev/null < /dev/null | tail -1 > $O/bench_head_f16.json

@@ -1,5 +1,5 @@
 """The ROLE contract of the PnP initialiser against vectors of the reference's `cv2_solver.solve` (tests/golden/gen_golden_ransac_cv2.py):
-shared by the CPU (oracle) and GPU (kernel) tests and exercised against a stand-in by tests/test_golden_generators.py.
+shared by the CPU (oracle) and GPU (kernel) tests.
 
 OpenCV's RANSAC cannot be matched hypothesis by hypothesis (its RNG, its EPnP).  What `test.py:59,120` needs from it, and what is checked:
   (1) validity: a pose the reference solves is solved here (the converse may differ on ill-posed rows: counted, bounded);

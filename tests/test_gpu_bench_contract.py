@@ -22,7 +22,7 @@ def _last_json(out):
 def test_single_gpu_line_has_the_contract_keys():
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--regions", "5", "--cpu-budget", "2",
-                          "--steady-batch", "4096"], capture_output=True, text=True, timeout=900)
+                          "--steady-batch", "4096", "--full"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _last_json(out.stdout)
     assert d["metric"] == base["metric"] and d["unit"] == "poses/s" and d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 3
@@ -88,7 +88,7 @@ def test_two_rank_control_flow_on_one_gpu():
     env = dict(os.environ, LC_BENCH_SHARE_GPU="1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3",
-                          "--regions", "5"], capture_output=True, text=True, timeout=900, env=env)
+                          "--regions", "5", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _last_json(out.stdout)
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["collective_backend"] == "gloo" and len(d["per_rank_ms_per_step"]) == 2
@@ -106,7 +106,7 @@ def test_gpus_2_starts_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher around it: the script starts the two ranks itself (the driver's command form)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["LC_BENCH_SHARE_GPU"] = "1"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3", "--regions", "5"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3", "--regions", "5", "--full"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -125,7 +125,7 @@ def test_gpus_8_on_one_shared_gpu_and_a_rank_that_dies():
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["LC_BENCH_SHARE_GPU"] = "1"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "3", "--regions", "5"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "3", "--regions", "5", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -175,3 +175,41 @@ def test_rccl_code_path_with_one_rank():
     d = _last_json(out.stdout)
     assert d["n_gpus"] == 1 and d["collective_backend"] == "nccl" and d["rccl_version"] and "rccl_error" not in d, (d.get("rccl_error"), out.stderr[-1500:])
     assert d["config"]["launch"] == "graph_region"  # the capture coexists with the RCCL group's watchdog thread
+
+
+def test_plain_line_is_lean_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run times exactly --steps steps in one region and carries only the headline; --dump-outputs writes the last step's
+    outputs, the same bits from run to run (seeded inputs, one launch form), and they are the pose unit's results."""
+    import numpy as np
+
+    runs = []
+    for i in range(2):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1500", "--warmup", "7",
+                              "--dump-outputs", str(tmp_path / f"run{i}")], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        runs.append(_last_json(out.stdout))
+    d = runs[0]
+    assert d["steps"] == 1500 and d["warmup"] == 7 and d["unit"] == "poses/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert abs(d["value"] - 256 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"] and d["config"]["launch"] == "graph_region"
+    assert d["timing"]["protocol"].startswith("1 regions of exactly 1500 steps")  # 1500 steps = one graph of 1000 nodes + one of 500
+    for k in ("roofline", "value_stream_order", "steady_state", "dense", "test_time", "head", "cpu_baseline", "strong"):
+        assert k not in d, k
+    names = {"loss": (256,), "d_pts2d": (256, 64, 2), "d_inv_std": (256, 64, 2), "d_pts3d": (256, 64, 3), "pnp_states": (256, 7),
+             "pnp_result_tr": (256,), "pnp_rets": (256,)}
+    assert sorted(os.listdir(tmp_path / "run0")) == sorted(f"{k}.npy" for k in names)
+    for k, shape in names.items():
+        a, b = np.load(tmp_path / "run0" / f"{k}.npy"), np.load(tmp_path / "run1" / f"{k}.npy")
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all() and np.array_equal(a, b), k
+    assert not np.load(tmp_path / "run0" / "pnp_rets.npy").any()
+    # the line's loss is the oracle's on the same seeded batch (seed = rank 0)
+    import torch
+
+    sys.path.insert(0, ROOT)
+    from lc_amd import synth
+    from oracle import lc_loss_oracle
+
+    b = {k: v.double() for k, v in synth.make_batch(256, 64, seed=0).items()}
+    ref, gu, _, _ = lc_loss_oracle.loss_and_grads(b["K"], b["pose"], b["pts3d"], b["pts2d"], b["inv_std"], None, b["bbox_3d"],
+                                                  grad_out=torch.full((256,), 1 / 256, dtype=torch.float64), want_pts3d=False)
+    assert np.abs(np.load(tmp_path / "run0" / "loss.npy") - ref.numpy()).max() < 1e-4
+    assert np.abs(np.load(tmp_path / "run0" / "d_pts2d.npy") - gu.numpy()).max() <= 1e-3 * np.abs(gu.numpy()).max()
