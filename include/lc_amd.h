@@ -437,6 +437,27 @@ int lc_xyz_bin_loss_counts(const void *logits, const unsigned char *gt_bits, con
                            void *stream);
 int lc_xyz_bin_loss_finish(const long long *counts, const float *bce_mean, int C, float momentum, float *histogram, float *loss,
                            float *bin_weights, void *stream);
+/* Label preparation of a training step (losses.py:68-139 annots_on_the_fly), two launches.
+ * lc_sym_select_f32: select_pose_2d / select_pose_3d (symmetry.py:8-56) of every chunk of a batch.  cand (Ktot,3,4): the candidate
+ *   chunks back to back; chunk c covers batch rows [chunk_rows[c], chunk_rows[c+1]) with chunk_k[c] candidates per row (HOST arrays of
+ *   nchunks + 1 and nchunks ints, nchunks <= 32, chunk_rows[0] = 0, chunk_rows[nchunks] = B).  mode 0 (2D): cam_K = out_K, pts_a = pts3d
+ *   (B,N,3), pts_b = predicted pts2d (B,N,2).  mode 1 (3D): cam_K = K_no_aug; pts_a = predicted points (B,N,3), or NULL to read the
+ *   continuous head xyz_map (B,3,H,W, map_dtype, batch stride map_bstride or 0) at the check pixels times noc_scale (B,3); pts_b = homo_z
+ *   at the points (B,N,3), or NULL to read homo_z (B,H,W,3) at the check pixels ck (B,N,2) int64 (x, y; negative values count from the
+ *   end).  N <= 1024.  Rt_best (B,3,4) <- the candidate of least mean error (torch.argmin: first index on ties, NaN first);
+ *   best_idx (B,) int32 <- its index within the row's candidates, or NULL.
+ * lc_label_targets_f32: xyz_gt (B,H,W,3) = R^T (K^-1 h - t) * msk_noc for Rt (B,3,4), cam_K (B,3,3), homo_z (B,H,W,3); then the targets of
+ *   xyz_to_nn_target (losses.py:49-67): the model transform xform (B,4,4) or NULL, / noc_scale (B,3), and noc_tgt (B,3,H,W) f32 and/or the
+ *   code planes bin_tgt (Gray code, planes 0-1 of each axis inverted when black_background) / bin_raw (B,n0+n1+n2,H,W) as bytes 0 / 1.
+ *   msk_noc as bytes or floats (at most one; none: no mask).  Every output may be NULL. */
+int lc_sym_select_f32(const float *cand, const int *chunk_rows, const int *chunk_k, int nchunks, int mode, const float *cam_K,
+                      const float *pts_a, const float *pts_b, const void *xyz_map, int map_dtype, long long map_bstride,
+                      const float *noc_scale, const float *homo_z, const long long *ck, int B, int N, int H, int W, float *Rt_best,
+                      int *best_idx, void *stream);
+int lc_label_targets_f32(const float *homo_z, const unsigned char *msk_noc_u8, const float *msk_noc_f32, const float *Rt,
+                         const float *cam_K, const float *noc_scale, const float *xform, int B, int H, int W, int n0, int n1, int n2,
+                         int black_background, float *xyz_gt, float *noc_tgt, unsigned char *bin_tgt, unsigned char *bin_raw,
+                         void *stream);
 /* The NormClipper pair (2h) on a gradient of any map type: the hooks sit on the heads' outputs
  * (losses.py:343-352), so under mixed precision the gradient they clip is 16-bit; read and written in place of a cast each way. */
 int lc_sqnorm(const void *x, int dtype, long long n, double *partials, unsigned *ticket, float *sq, int accumulate,

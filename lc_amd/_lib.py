@@ -63,6 +63,10 @@ _SIGNATURES = {
     "lc_xyz_bin_loss_counts": (c_int, [c_void_p] * 3 + [c_int, ctypes.c_longlong, ctypes.c_longlong] + [c_int] * 3 + [c_void_p] * 5),
     "lc_xyz_bin_loss_finish": (c_int, [c_void_p, c_void_p, c_int, c_float] + [c_void_p] * 4),
     "lc_xyz_bin_loss_bwd2": (c_int, [c_void_p] * 5 + [c_int, ctypes.c_longlong, ctypes.c_longlong] + [c_int] * 3 + [c_void_p] * 2),
+    # label preparation (lc_labels.hip): the chunk table is two HOST int arrays
+    "lc_sym_select_f32": (c_int, [c_void_p, _I, _I, c_int, c_int] + [c_void_p] * 4 + [c_int, ctypes.c_longlong] + [c_void_p] * 3 + [c_int] * 4 +
+                          [c_void_p] * 3),
+    "lc_label_targets_f32": (c_int, [c_void_p] * 7 + [c_int] * 7 + [c_void_p] * 5),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -716,5 +716,68 @@ int lc_xyz_bin_loss_bwd2(const void* logits, const unsigned char* gt_bits, const
     return lc::launch_xyz_bin_loss_bwd(p, static_cast<hipStream_t>(stream)) ? fail(11, "code loss backward launch failed") : 0;
 }
 
+int lc_sym_select_f32(const float* cand, const int* chunk_rows, const int* chunk_k, int nchunks, int mode, const float* cam_K, const float* pts_a,
+                      const float* pts_b, const void* xyz_map, int map_dtype, long long map_bstride, const float* noc_scale, const float* homo_z,
+                      const long long* ck, int B, int N, int H, int W, float* Rt_best, int* best_idx, void* stream) {
+    if (B < 0 || N <= 0 || H < 0 || W < 0) return fail(1, "bad size");
+    if (N > lc::kSymMaxPoints) return fail(1, "more than 1024 check points per sample");
+    if (mode != 0 && mode != 1) return fail(1, "mode must be 0 (2D) or 1 (3D)");
+    if (nchunks <= 0 || nchunks > lc::kSymMaxChunks) return fail(1, "between 1 and 32 candidate chunks");
+    if (!chunk_rows || !chunk_k) return fail(1, "null chunk table");
+    if (chunk_rows[0] != 0 || chunk_rows[nchunks] != B) return fail(1, "chunk rows must start at 0 and end at B");
+    lc::SymSelectParams p{};
+    long long ktot = 0;
+    for (int c = 0; c < nchunks; ++c) {
+        if (chunk_rows[c + 1] < chunk_rows[c]) return fail(1, "chunk rows must not decrease");
+        if (chunk_k[c] <= 0) return fail(1, "every chunk needs at least one candidate");
+        p.chunk_row[c] = chunk_rows[c];
+        p.chunk_k[c] = chunk_k[c];
+        p.chunk_off[c] = (int)ktot;
+        ktot += (long long)(chunk_rows[c + 1] - chunk_rows[c]) * chunk_k[c];
+        if (ktot >= (1ll << 31) / 12) return fail(1, "too many candidates");
+    }
+    p.chunk_row[nchunks] = B;
+    if (B == 0) return 0;
+    if (!cand || !cam_K || !Rt_best) return fail(1, "null pointer");
+    if (mode == 0) {
+        if (!pts_a || !pts_b) return fail(1, "2D mode needs pts3d and pts2d");
+    } else {
+        if (!pts_a && (!xyz_map || !noc_scale)) return fail(1, "3D mode needs the predicted points or the xyz map with noc_scale");
+        if (!pts_b && !homo_z) return fail(1, "3D mode needs homo_z at the points or the homo_z map");
+        if (!pts_a || !pts_b) {
+            if (!ck) return fail(1, "reading a map needs the check pixels");
+            if (H <= 0 || W <= 0) return fail(1, "bad map size");
+            if ((long long)B * H * W * 3 >= (1ll << 31)) return fail(1, "maps of 2^31 elements or more");
+        }
+        if (!pts_a) {
+            if (map_dtype < 0 || map_dtype > 2) return fail(1, "map_dtype must be LC_F32, LC_F16 or LC_BF16");
+            if (map_bstride < 0 || (map_bstride && map_bstride < 3ll * H * W)) return fail(1, "batch stride smaller than a sample");
+        }
+    }
+    p.nchunks = nchunks; p.cand = cand; p.mode = mode; p.cam_K = cam_K; p.pts_a = pts_a; p.pts_b = pts_b;
+    p.xyz_map = xyz_map; p.map_dtype = map_dtype; p.map_bs = map_bstride ? map_bstride : 3ll * H * W; p.noc_scale = noc_scale;
+    p.homo_z = homo_z; p.ck = ck; p.B = B; p.N = N; p.H = H; p.W = W; p.Rt_best = Rt_best; p.best_idx = best_idx;
+    return lc::launch_sym_select(p, static_cast<hipStream_t>(stream)) ? fail(11, "symmetry selection launch failed") : 0;
+}
+
+int lc_label_targets_f32(const float* homo_z, const unsigned char* msk_noc_u8, const float* msk_noc_f32, const float* Rt, const float* cam_K,
+                         const float* noc_scale, const float* xform, int B, int H, int W, int n0, int n1, int n2, int black_background,
+                         float* xyz_gt, float* noc_tgt, unsigned char* bin_tgt, unsigned char* bin_raw, void* stream) {
+    if (B < 0 || H <= 0 || W <= 0) return fail(1, "bad size");
+    const bool bits = bin_tgt || bin_raw;
+    if (bits && (n0 < 1 || n1 < 1 || n2 < 1 || n0 > 24 || n1 > 24 || n2 > 24)) return fail(1, "bit counts must lie in 1..24");
+    const long long C = bits ? (long long)n0 + n1 + n2 : 3;
+    if ((long long)B * H * W * (C > 3 ? C : 3) >= (1ll << 31)) return fail(1, "outputs of 2^31 elements or more");
+    if (msk_noc_u8 && msk_noc_f32) return fail(1, "at most one mask form");
+    if (!xyz_gt && !noc_tgt && !bits) return fail(1, "no output");
+    if (B == 0) return 0;
+    if (!homo_z || !Rt || !cam_K) return fail(1, "null pointer");
+    if ((noc_tgt || bits) && !noc_scale) return fail(1, "the targets need noc_scale");
+    LC_REQUIRE_ALIGNED(4, homo_z, Rt, cam_K, noc_scale, xform, xyz_gt, noc_tgt, msk_noc_f32);
+    lc::LabelParams p{homo_z, msk_noc_u8, msk_noc_f32, Rt, cam_K, noc_scale, xform, xyz_gt, noc_tgt, bin_tgt, bin_raw, B, H * W, {n0, n1, n2},
+                      black_background ? 1 : 0};
+    return lc::launch_label_targets(p, static_cast<hipStream_t>(stream)) ? fail(11, "label targets launch failed") : 0;
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

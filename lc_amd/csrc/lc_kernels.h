@@ -363,4 +363,50 @@ int launch_dense_select(const SelectParams& p, hipStream_t stream);
 // front end + selection in one launch (test time, N <= 1024): the input arrays of `p` are unused (null), `d` names the maps
 int launch_dense_frontend_select(const SelectParams& p, const DenseParams& d, hipStream_t stream);  // 3: N > 1024
 
+// Label preparation (lc_labels.hip; losses.py:68-139 annots_on_the_fly).  Symmetry candidate selection: row b of the batch takes the
+// candidates of its chunk (contiguous batch rows with the same candidate count, dataset.py:351-362); chunk c covers rows
+// [chunk_row[c], chunk_row[c+1]) with chunk_k[c] candidates each, starting at candidate chunk_off[c] of `cand`.
+constexpr int kSymMaxChunks = 32;
+constexpr int kSymMaxPoints = 1024;
+struct SymSelectParams {
+    const float* cand;            // (Ktot,3,4) all candidates of the batch, row-major [R | t]
+    int nchunks;
+    int chunk_row[kSymMaxChunks + 1];
+    int chunk_k[kSymMaxChunks];
+    int chunk_off[kSymMaxChunks];
+    int mode;                     // 0: 2D (select_pose_2d), 1: 3D (select_pose_3d)
+    const float* cam_K;           // (B,3,3): out_K (2D) / K_no_aug (3D)
+    const float* pts_a;           // 2D: ground-truth pts3d (B,N,3); 3D: predicted points (B,N,3), or null (read from xyz_map)
+    const float* pts_b;           // 2D: predicted pts2d (B,N,2); 3D: homo_z at the points (B,N,3), or null (read from homo_z)
+    const void* xyz_map;          // 3D, continuous head: (B,3,H,W) xyz_noc of element type map_dtype, times noc_scale (B,3)
+    int map_dtype;
+    long long map_bs;             // elements between samples of xyz_map
+    const float* noc_scale;
+    const float* homo_z;          // 3D: (B,H,W,3) homo_z_out
+    const long long* ck;          // (B,N,2) check pixels (x, y); negative values count from the end like Python indices
+    int B, N, H, W;
+    float* Rt_best;               // (B,3,4)
+    int* best_idx;                // (B,) index within the row's candidates, or null
+};
+int launch_sym_select(const SymSelectParams& p, hipStream_t stream);
+
+// Label targets: xyz_gt = R^T (K^-1 h - t) * m over B x H x W, then the network targets of xyz_to_nn_target (losses.py:49-67)
+struct LabelParams {
+    const float* homo_z;          // (B,H,W,3)
+    const unsigned char* msk_u8;  // (B,H,W) msk_noc as bytes, or
+    const float* msk_f32;         // (B,H,W) as floats; both null: no mask (xyz_from_homo_z alone)
+    const float* Rt;              // (B,3,4) pose [R | t]
+    const float* cam_K;           // (B,3,3)
+    const float* noc_scale;       // (B,3), targets only
+    const float* xform;           // (B,4,4) model transform, or null
+    float* xyz_gt;                // (B,H,W,3) or null
+    float* noc_tgt;               // (B,3,H,W) continuous target, or null
+    unsigned char* bin_tgt;       // (B,C,H,W) Gray-coded bits (bool), or null
+    unsigned char* bin_raw;       // (B,C,H,W) plain binary bits (bool), or null
+    int B, HW;
+    int bits[3];
+    int black;                    // invert code planes 0-1 of every axis (floatbits._black_background)
+};
+int launch_label_targets(const LabelParams& p, hipStream_t stream);
+
 }  // namespace lc

@@ -13,6 +13,10 @@
     lib.utils.grad.NormClipper     -> lc_amd.grad.NormClipper             (same constructor and `max_norm` buffer; also the name in `losses`)
     losses.Loss_fn.sparse_kpt_loss / .dense_pose_loss -> the fused-launch methods of lc_amd.losses.Loss_fn (they only use the
                                                           attributes the reference's own Loss_fn instance has)
+
+Opt-in (`install(native_labels=True)`, or `python -m lc_amd.dropin --native-labels train.py ...`): label preparation on the device --
+    losses.annots_on_the_fly / selete_best_pose / xyz_from_homo_z, symmetry.select_pose_2d / select_pose_3d -> lc_amd.labels
+(`train.py:58,116` look the names up on the module at call time).  Without it the reference's own label preparation runs.
 """
 from __future__ import annotations
 
@@ -22,9 +26,10 @@ import sys
 import types
 
 
-def install(patch_ptnet: bool = True, gpu_initialiser=None) -> dict:
+def install(patch_ptnet: bool = True, gpu_initialiser=None, native_labels: bool = False) -> dict:
     """gpu_initialiser: True = also register the RANSAC-P3P kernel as `lib.pnp.cv2_solver` (same `solve` surface,
-    `test.py:59,120`); None (default) = only when OpenCV cannot be imported, so that `test.py` runs without it."""
+    `test.py:59,120`); None (default) = only when OpenCV cannot be imported, so that `test.py` runs without it.
+    native_labels: also rebind the reference's label-preparation names to lc_amd.labels (done["labels"])."""
     from . import cov_mixed as cm
     from . import ptnet as head
     from .pnp import cer_solver, gpu_solver, pnp_ceres
@@ -96,18 +101,39 @@ def install(patch_ptnet: bool = True, gpu_initialiser=None) -> dict:
             done["ptnet"] = True
         except Exception:
             done["ptnet"] = False
+    if native_labels:
+        done["labels"] = _install_labels()
     return done
+
+
+_LABEL_NAMES = {"losses": ("annots_on_the_fly", "selete_best_pose", "xyz_from_homo_z"), "symmetry": ("select_pose_2d", "select_pose_3d")}
+
+
+def _install_labels() -> bool:
+    from . import labels
+
+    try:
+        mods = {name: importlib.import_module(name) for name in _LABEL_NAMES}
+    except Exception:  # the reference's modules need scipy etc.; absent pieces are the caller's problem
+        return False
+    for name, attrs in _LABEL_NAMES.items():
+        for attr in attrs:
+            setattr(mods[name], attr, getattr(labels, attr))
+    return True
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
+    native_labels = bool(argv) and argv[0] == "--native-labels"
+    if native_labels:
+        argv = argv[1:]
     if not argv:
         raise SystemExit(__doc__)
     script = argv[0]
     import os
 
     sys.path.insert(0, os.path.dirname(os.path.abspath(script)))
-    print("lc_amd.dropin:", install(), file=sys.stderr)
+    print("lc_amd.dropin:", install(native_labels=native_labels), file=sys.stderr)
     sys.argv = argv
     runpy.run_path(script, run_name="__main__")
 
