@@ -203,3 +203,91 @@ def test_strided_training_decode_launch_forms(H, W, sample, tl, bits, masked):
         assert torch.equal(oh, of)
         (gh,), (gf,) = torch.autograd.grad(oh, xh, ct.to(dev)), torch.autograd.grad(of, xf, ct.to(dev))
         assert gh.dtype == dt and torch.equal(gh, gf.to(dt))
+
+
+def _code_case(g, B, H, W, bits):
+    from lc_amd import floatbits as fb
+
+    noc = torch.rand(B, H, W, 3, generator=g) * 2 - 1
+    mod, raw = fb.nn_noc2target(noc, bits)
+    lg = (mod.float() * 2 - 1) * (torch.rand(B, sum(bits), H, W, generator=g) * 3 + 0.1)
+    lg = torch.where(torch.rand(lg.shape, generator=g) < 0.15, -lg, lg)
+    msk = torch.rand(B, H, W, generator=g) > 0.3
+    return lg, raw, msk
+
+
+# (sample, rows per tile) -> fp32 (W, left), 16-bit (W, left).  launch_bits_decode_gt_bwd: E = 16 bytes / element, per_row = W / E pieces
+# of a row (dividing 256), Wn = ceil((W - left) / sample); rows per tile = the largest R <= 4 with ceil(R / sample) Wn 3 <= 256 and
+# R per_row <= 256.  (2, 3) has no shape: R = 3 and 4 give the same ceil(R / 2), and no per_row dividing 256 lies in (64, 256 / 3].
+TILE_FORMS = {
+    (2, 1): ((1024, 900), (2048, 1900)),  # per_row = 256: one row per tile; a left margin keeps Wn <= 85
+    (2, 2): ((128, 0), (128, 0)),
+    (2, 4): ((64, 0), (64, 0)),
+    (3, 1): ((1024, 900), (2048, 1900)),
+    (3, 2): ((512, 300), (1024, 800)),  # per_row = 128
+    (3, 3): ((128, 0), (128, 0)),  # zlmo: 128 wide, every third pixel
+    (3, 4): ((64, 0), (64, 0)),
+}
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16], ids=["f32", "f16", "bf16"])
+@pytest.mark.parametrize("S,RR", sorted(TILE_FORMS), ids=[f"S{s}_RR{r}" for s, r in sorted(TILE_FORMS)])
+def test_bits_tile_backward_forms(S, RR, dtype):
+    """Each lc_bits_decode_gt_bwd_tile_kernel<E, T, S, RR> the launcher can pick: a strided subset (sample S, a row offset of 1 and the
+    listed column offset) whose row width gives RR rows per tile, over seven rows (a partial last tile).  fp32 against the fp64 oracle;
+    fp16 / bf16 maps against the fp32 kernel on the up-cast logits: the same decode, the gradient rounded to the map's type."""
+    from lc_amd import floatbits as fb
+    from oracle import floatbits_oracle as orc
+
+    W, left = TILE_FORMS[(S, RR)][dtype != torch.float32]
+    E = 4 if dtype == torch.float32 else 8
+    Wn, per_row = (W - left + S - 1) // S, W // E
+    assert 256 % per_row == 0 and max(R for R in range(1, 5) if (R + S - 1) // S * Wn * 3 <= 256 and R * per_row <= 256) == RR
+    g = torch.Generator().manual_seed(W * 10 + S)
+    B, H, bits = 2, 7, [5, 4, 3]
+    lg, raw, msk = _code_case(g, B, H, W, bits)
+    lg = lg.to(dtype).float()
+    dev = torch.device("cuda:0")
+    tl = (1, left)
+    x = lg.to(dtype).to(dev).requires_grad_(True)
+    out = fb.decode_with_gt_strided(x, raw.to(dev), bits, msk.to(dev), sample=S, top_left=tl)
+    ct = torch.randn(out.shape, generator=g)
+    (gk,) = torch.autograd.grad(out, x, ct.to(dev))
+    assert gk.dtype == dtype
+    if dtype != torch.float32:
+        x32 = lg.to(dev).requires_grad_(True)
+        out32 = fb.decode_with_gt_strided(x32, raw.to(dev), bits, msk.to(dev), sample=S, top_left=tl)
+        (g32,) = torch.autograd.grad(out32, x32, ct.to(dev))
+        assert torch.equal(out, out32) and torch.equal(gk, g32.to(dtype))
+        return
+    x64 = lg.double().requires_grad_(True)
+    sl = (Ellipsis, slice(tl[0], None, S), slice(tl[1], None, S))
+    ref = orc.nn_logits2noc_with_gt(x64[sl], raw[sl], bits, msk[sl]).flatten(1, 2)
+    assert out.shape == ref.shape and rel_err(out.detach().cpu(), ref.detach()) <= 2e-6
+    (go,) = torch.autograd.grad(ref, x64, ct.double())
+    assert rel_err(gk.cpu(), go) <= 5e-6
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16], ids=["f32", "f16", "bf16"])
+def test_bits_more_than_65535_samples_take_the_generic_forward(dtype):
+    """B = 65536 1 x 1 maps: the grid's y dimension cannot hold the batch, so the strided forward leaves the wide kernel
+    (lc_bits_decode_gt_fwd_wide_kernel: B <= 65535) for lc_bits_decode_gt_fwd_kernel<1, T>, and the backward takes
+    lc_bits_decode_gt_bwd_kernel<1, T>.  Against the fp64 oracle."""
+    from lc_amd import floatbits as fb
+    from oracle import floatbits_oracle as orc
+
+    g = torch.Generator().manual_seed(65536)
+    B, bits = 65536, [3, 2, 2]
+    lg, raw, msk = _code_case(g, B, 1, 1, bits)
+    lg = lg.to(dtype).float()
+    dev = torch.device("cuda:0")
+    x = lg.to(dtype).to(dev).requires_grad_(True)
+    out = fb.nn_logits2noc_with_gt(x, raw.to(dev), bits, msk.to(dev))
+    ct = torch.randn(out.shape, generator=g)
+    (gk,) = torch.autograd.grad(out, x, ct.to(dev))
+    x64 = lg.double().requires_grad_(True)
+    ref = orc.nn_logits2noc_with_gt(x64, raw, bits, msk)
+    assert rel_err(out.detach().cpu(), ref.detach()) <= 2e-6
+    (go,) = torch.autograd.grad(ref, x64, ct.double())
+    rnd = {torch.float32: 0.0, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}[dtype]  # half an ulp of the gradient's type, relative
+    assert ((gk.cpu().double() - go).abs() <= 5e-6 * go.abs().max() + rnd * go.abs()).all()

@@ -138,3 +138,135 @@ def test_head_vs_golden_survey_sizes(path):
     check_compact(z, mean.detach(), std.detach(), g, probe, 2e-4, 2e-6, tol_map=2e-4)  # same bounds as test_head_vs_golden (fp32 kernel, __expf)
     # the fp32 reference run sits as close to the fp64 one as the kernel does
     assert (torch.from_numpy(z["f32_mean"]).double() - torch.from_numpy(z["f64_mean"])).abs().max().item() <= 2e-4
+
+
+def _map_at(vals, dtype, off):
+    """vals (fp32, CPU) in `dtype` in a fresh device buffer at storage offset `off` elements, as a contiguous view (ptnet keeps it in place)."""
+    buf = torch.zeros(vals.numel() + off, dtype=dtype, device="cuda:0")
+    x = buf[off:].view(vals.shape)
+    x.copy_(vals.to(dtype).to("cuda:0"))
+    return x
+
+
+def _head_fwd_bwd(x, prob, ct_m, ct_s):
+    from lc_amd.ptnet import spatial_softargmax_2d_std, softargmax_2d_std
+
+    x = x.detach().requires_grad_(True)
+    mean, std = (softargmax_2d_std if prob else spatial_softargmax_2d_std)(x)
+    (g,) = torch.autograd.grad((mean * ct_m).sum() + (std * ct_s).sum(), x)
+    return mean.detach(), std.detach(), g
+
+
+# (H, W, storage offset) -> lc_head_fwd_kernel<T, NV, VEC>: VEC = 4 needs W % 4 == 0 and the map aligned to four elements (else 1),
+# NV = the power of two >= ceil(H W / (256 VEC)); 64 x 64 and 128 x 128 maps with VEC = 4 take the dedicated kernels instead
+HEAD_FORMS = {
+    (1, 4): (24, 40, 0), (2, 4): (32, 48, 0), (4, 4): (48, 60, 0), (8, 4): (80, 96, 0),
+    (16, 4): (100, 160, 0),  # 65 KB of LDS: above the 48 KB default, hipFuncSetAttribute raises the limit
+    (32, 4): (176, 176, 0),  # 123 KB of LDS
+    (1, 1): (7, 9, 0), (2, 1): (15, 25, 0), (4, 1): (30, 33, 0), (8, 1): (32, 48, 1), (16, 1): (50, 61, 0), (32, 1): (64, 100, 1),
+}
+
+
+@pytest.mark.parametrize("prob", [False, True], ids=["logits", "prob"])
+@pytest.mark.parametrize("nv,vec", sorted(HEAD_FORMS), ids=[f"NV{n}_VEC{v}" for n, v in sorted(HEAD_FORMS)])
+def test_head_fwd_forms_fp32_vs_fp64(nv, vec, prob):
+    """Every (NV, VEC) form of the generic single-pass forward on fp32 maps, logits and probabilities in, forward and backward against
+    the float64 restatement (oracle/softargmax_oracle.py).  The backward forms these shapes reach: lc_head_bwd_kernel<float, 4, false>
+    (W % 4 == 0; none of these widths divides 1024, so the column-fixed form is not taken) and <float, 1, false> (W % 4 != 0 or a misaligned
+    map)."""
+    from oracle import softargmax_oracle as orc
+
+    H, W, off = HEAD_FORMS[(nv, vec)]
+    assert (4 if (W % 4 == 0 and off % 4 == 0) else 1) == vec and max(1, 1 << ((H * W + 256 * vec - 1) // (256 * vec) - 1).bit_length()) == nv
+    g = torch.Generator().manual_seed(H * W + prob)
+    lg = torch.randn(2, 3, H, W, generator=g) * 3
+    vals = lg.flatten(-2).softmax(-1).reshape(lg.shape) if prob else lg
+    ct_m, ct_s = torch.randn(2, 3, 2, generator=g), torch.randn(2, 3, 2, generator=g)
+    mean, std, gx = _head_fwd_bwd(_map_at(vals, torch.float32, off), prob, ct_m.to("cuda:0"), ct_s.to("cuda:0"))
+    v64 = vals.double().requires_grad_(True)
+    m64, s64 = (orc.softargmax_2d_std if prob else orc.spatial_softargmax_2d_std)(v64)
+    (g64,) = torch.autograd.grad((m64 * ct_m.double()).sum() + (s64 * ct_s.double()).sum(), v64)
+    assert (mean.cpu().double() - m64.detach()).abs().max().item() <= 3e-4
+    assert (std.cpu().double() - s64.detach()).abs().max().item() <= 3e-4
+    assert rel_err(gx.cpu(), g64) <= 3e-4
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+@pytest.mark.parametrize("prob", [False, True], ids=["logits", "prob"])
+@pytest.mark.parametrize("nv,vec", sorted(HEAD_FORMS), ids=[f"NV{n}_VEC{v}" for n, v in sorted(HEAD_FORMS)])
+def test_head_fwd_forms_16bit_match_the_fp32_kernel(nv, vec, prob, dtype):
+    """The same (NV, VEC) forms on fp16 / bf16 maps: statistics identical to the fp32 kernel's on the up-cast values at the same storage
+    offset (the same form), gradient = that fp32 gradient rounded to the map's type.  16-bit backward forms: <T, 8, false> (W % 8 == 0, none
+    of these widths divides 2048), <T, 4, false> (W % 8 == 4) and <T, 1, false>."""
+    H, W, off = HEAD_FORMS[(nv, vec)]
+    g = torch.Generator().manual_seed(H * W + 7 * prob)
+    lg = torch.randn(2, 3, H, W, generator=g) * 3
+    vals = (lg.flatten(-2).softmax(-1).reshape(lg.shape) if prob else lg).to(dtype).float()
+    ct_m, ct_s = torch.randn(2, 3, 2, generator=g).to("cuda:0"), torch.randn(2, 3, 2, generator=g).to("cuda:0")
+    m16, s16, g16 = _head_fwd_bwd(_map_at(vals, dtype, off), prob, ct_m, ct_s)
+    m32, s32, g32 = _head_fwd_bwd(_map_at(vals, torch.float32, off), prob, ct_m, ct_s)
+    assert torch.equal(m16, m32) and torch.equal(s16, s32)
+    assert g16.dtype == dtype and torch.equal(g16, g32.to(dtype))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16], ids=["f32", "f16", "bf16"])
+@pytest.mark.parametrize("prob", [False, True], ids=["logits", "prob"])
+@pytest.mark.parametrize("off", [4, 1], ids=["off4", "off1"])
+def test_head_64x64_forms_at_offset_views(off, prob, dtype):
+    """64 x 64 maps at a storage offset leave the aligned paths: 16-bit maps at offset 4 (8 bytes) take lc_head_fwd_rows_kernel<T, 16, 4>
+    (float4-able but not 16-byte aligned) and lc_head_bwd_kernel<T, 4, .> instead of <T, 8, .>; offset 1 takes the generic forward
+    <T, 16, 1> and the backward <T, 1, false>; fp32 maps at offset 4 (16 bytes) stay on the one-wave-per-map forward and <float, 4, .>.
+    Against the fp64 restatement on the (exactly up-cast) map values; a 16-bit gradient may differ from it by its rounding to the type."""
+    from oracle import softargmax_oracle as orc
+
+    g = torch.Generator().manual_seed(off + 10 * prob)
+    lg = torch.randn(3, 2, 64, 64, generator=g) * 3
+    vals = (lg.flatten(-2).softmax(-1).reshape(lg.shape) if prob else lg).to(dtype).float()
+    ct_m, ct_s = torch.randn(3, 2, 2, generator=g), torch.randn(3, 2, 2, generator=g)
+    m, s, gx = _head_fwd_bwd(_map_at(vals, dtype, off), prob, ct_m.to("cuda:0"), ct_s.to("cuda:0"))
+    v64 = vals.double().requires_grad_(True)
+    m64, s64 = (orc.softargmax_2d_std if prob else orc.spatial_softargmax_2d_std)(v64)
+    (g64,) = torch.autograd.grad((m64 * ct_m.double()).sum() + (s64 * ct_s.double()).sum(), v64)
+    assert (m.cpu().double() - m64.detach()).abs().max().item() <= 3e-4
+    assert (s.cpu().double() - s64.detach()).abs().max().item() <= 3e-4
+    assert gx.dtype == dtype
+    rnd = {torch.float32: 0.0, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}[dtype]  # half an ulp, relative
+    assert ((gx.cpu().double() - g64).abs() <= 3e-4 * g64.abs().max() + rnd * g64.abs()).all()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_head_map_beyond_the_single_pass_limit_is_an_error(dtype):
+    """200 x 200: H (W + 1) + W + H + 8 floats of LDS = 159 KB fit, but 40000 elements need NV = 64 > 32 (VEC = 4); 180 x 230 needs
+    164 KB > 160 KB.  launch_head_fwd_t returns 3, the wrapper raises -- never a partial result."""
+    from lc_amd.ptnet import spatial_softargmax_2d_std
+
+    for H, W in ((200, 200), (180, 230)):
+        x = torch.zeros(1, 1, H, W, dtype=dtype, device="cuda:0")
+        with pytest.raises(RuntimeError, match=r"code 3\): map too large for the single-pass"):
+            spatial_softargmax_2d_std(x)
+
+
+@pytest.mark.parametrize("prob", [False, True], ids=["logits", "prob"])
+def test_head_rows_kernel_with_misaligned_outputs(prob):
+    """fp32 64 x 64 maps reach lc_head_fwd_rows_kernel<float, 16, 4> only when an output is not aligned for the one-wave-per-map kernel's
+    wide stores (mean / std to 8 bytes, stats to 16): the C ABI called with outputs at an offset of one float, against the fp64 restatement
+    and against the wrapper's (aligned) run of the same maps."""
+    from lc_amd import _lib
+    from lc_amd.ptnet import softargmax_2d_std, spatial_softargmax_2d_std
+    from oracle import softargmax_oracle as orc
+
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(64 + prob)
+    lg = torch.randn(3, 2, 64, 64, generator=g) * 3
+    vals = lg.flatten(-2).softmax(-1).reshape(lg.shape) if prob else lg
+    x = vals.to(dev)
+    M = 6
+    buf = torch.zeros(1 + 2 * M + 1 + 2 * M + 1 + 4 * M, device=dev)
+    mean, std, stats = buf[1:1 + 2 * M], buf[2 + 2 * M:2 + 4 * M], buf[3 + 4 * M:3 + 8 * M]
+    rc = _lib.load().lc_softargmax2d_fwd(_lib.ptr(x), 0, M, 64, 64, int(prob), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(stats), _lib.stream_ptr(dev))
+    _lib.check(rc, "lc_softargmax2d_fwd")
+    m64, s64 = (orc.softargmax_2d_std if prob else orc.spatial_softargmax_2d_std)(vals.double())
+    assert (mean.view(3, 2, 2).cpu().double() - m64).abs().max().item() <= 3e-4
+    assert (std.view(3, 2, 2).cpu().double() - s64).abs().max().item() <= 3e-4
+    ma, sa = (softargmax_2d_std if prob else spatial_softargmax_2d_std)(x)
+    assert (mean.view(3, 2, 2) - ma).abs().max().item() <= 1e-4 and (std.view(3, 2, 2) - sa).abs().max().item() <= 1e-4

@@ -304,3 +304,146 @@ def test_zlmo_shape_feeds_loss_fn(sym):
         assert (x is None) == (y is None)
         if x is not None:
             assert ((x - y).abs().max() <= 1e-6 * y.abs().max()).item()
+
+
+def _posed_case(gen, B, K, N, mode):
+    """_random_case whose observations come from candidate pose P0 (row b's pose), so copies of P0 are exact ties at error ~0."""
+    cand, Kc, a, b = _random_case(gen, B, K, N, mode)
+    P0 = cand[:, 0].double()
+    R0, t0 = P0[..., :3], P0[..., 3]
+    if mode == 0:
+        h = torch.einsum("bij,bnj->bni", Kc.double(), torch.einsum("bij,bnj->bni", R0, a.double()) + t0[:, None])
+        b = (h[..., :2] / h[..., 2:3]).float()
+    else:
+        q = torch.einsum("bij,bnj->bni", torch.linalg.inv(Kc.double()), b.double())
+        a = torch.einsum("bji,bnj->bni", R0, q - t0[:, None]).float()
+    return cand, Kc, a, b, P0.float()
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("N", [65, 128, 257, 512])
+def test_selection_points_per_lane_2_and_8_vs_fp64_oracle(mode, N):
+    """N = 65 / 128 select lc_sym_select_kernel<2, 512> and N = 257 / 512 select <8, 512> (launch_sym_select: PPL = the smallest of
+    1, 2, 4, 8 with N <= 64 PPL, 512 threads), with the padded lanes of the last wave at N = 65 and 257.  Against the fp64 oracle,
+    with an exact tie (first index wins) and a NaN candidate (its first occurrence wins)."""
+    from lc_amd.labels import _select
+
+    gen = torch.Generator().manual_seed(30 + N + mode)
+    B, K = 4, 96
+    cand, Kc, a, b, P0 = _posed_case(gen, B, K, N, mode)
+    cand[1, 40] = P0[1]
+    cand[1, 70] = P0[1]  # row 1: the pose at 40 and 70 (and 0): index 0
+    cand[2, 0] = cand[2, 1]
+    cand[2, 50, 0, 0] = float("nan")
+    cand[2, 80, 1, 1] = float("nan")  # row 2: the first NaN wins
+    Rt, idx = _select(mode, [cand.to(DEV)], Kc.to(DEV), N, pts_a=a.to(DEV), pts_b=b.to(DEV))
+    errs, want = O.select(mode, Kc.double(), a.double(), b.double(), [cand.double()])
+    idx = idx.cpu().long()
+    _acceptable(errs, idx)
+    clear = torch.tensor(_clear(errs))
+    assert torch.equal(idx[clear], want[clear])
+    assert torch.equal(Rt.cpu().view(torch.int32), cand[torch.arange(B), idx].view(torch.int32))  # bitwise: NaN entries included
+    assert int(idx[1]) == 0 and int(idx[2]) == 50
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("K", [1024, 1025, 1500])
+def test_selection_beyond_the_lds_candidate_limit_vs_fp64_oracle(mode, K):
+    """K > 1024 candidates per row are walked from global memory (lc_labels.hip: staged = K > 1 && K <= kSelLdsCands); K = 1024 is the
+    last staged row.  Exact ties and NaN candidates on both sides of candidate 1024: row 0 holds the pose at 1010 and 1020 (1010 wins),
+    row 1 at 1010 and K-1 (1010 wins), row 2 only beyond the limit (K-1 wins when K > 1024), row 3 a NaN at 1000 and K-1 (1000 wins),
+    row 4 a NaN only at K-1 (it wins)."""
+    from lc_amd.labels import _select
+
+    gen = torch.Generator().manual_seed(K + mode)
+    B, N = 5, 64
+    cand, Kc, a, b, P0 = _posed_case(gen, B, K, N, mode)
+    cand[:, 0] = cand[:, 1]  # P0 itself is not a candidate of any row unless placed
+    cand[0, 1010], cand[0, 1020] = P0[0], P0[0]
+    cand[1, 1010], cand[1, K - 1] = P0[1], P0[1]
+    cand[2, K - 1] = P0[2]
+    cand[3, 1000, 0, 0] = float("nan")
+    cand[3, K - 1, 2, 2] = float("nan")
+    cand[4, K - 1, 0, 1] = float("nan")
+    Rt, idx = _select(mode, [cand.to(DEV)], Kc.to(DEV), N, pts_a=a.to(DEV), pts_b=b.to(DEV))
+    errs, want = O.select(mode, Kc.double(), a.double(), b.double(), [cand.double()])
+    idx = idx.cpu().long()
+    _acceptable(errs, idx)
+    clear = torch.tensor(_clear(errs))
+    assert torch.equal(idx[clear], want[clear])
+    assert torch.equal(Rt.cpu().view(torch.int32), cand[torch.arange(B), idx].view(torch.int32))
+    assert idx[:5].tolist() == [1010, 1010, K - 1, 1000, K - 1]
+
+
+def _label_inputs(gen, B, H, W):
+    K = torch.tensor([[90.0, 0.3, W / 2], [0, 85, H / 2], [0, 0, 1]]).expand(B, 3, 3).contiguous()
+    R = torch.linalg.qr(torch.randn(B, 3, 3, generator=gen, dtype=torch.float64))[0]
+    R = (R * torch.sign(torch.det(R))[:, None, None]).float()
+    t = torch.cat((torch.randn(B, 2, generator=gen) * 5, 600 + torch.rand(B, 1, generator=gen) * 50), -1)
+    v, u = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
+    z = t[:, 2, None, None] + torch.rand(B, H, W, generator=gen) * 60 - 30
+    hz = torch.stack((u * z, v * z, z), -1)
+    msk = torch.rand(B, H, W, generator=gen) > 0.25
+    T = torch.eye(4).expand(B, 4, 4).contiguous().clone()
+    T[:, :3, 3] = torch.randn(B, 3, generator=gen) * 3
+    sc = torch.full((B, 3), 40.0) + torch.rand(B, 3, generator=gen) * 10
+    return hz, torch.cat((R, t[..., None]), -1), K, msk, sc, T
+
+
+def _at_offset(t, off):
+    """t's values in a fresh device buffer at storage offset `off` elements (a contiguous view: _f32 / .contiguous() keep it in place)."""
+    buf = torch.zeros(t.numel() + off, dtype=t.dtype, device=DEV)
+    v = buf[off:].view(t.shape)
+    v.copy_(t.to(DEV))
+    return v
+
+
+@pytest.mark.parametrize("bits", [None, (7, 6, 5)], ids=["noc", "code"])
+@pytest.mark.parametrize("H,W", [(12, 13), (11, 13)], ids=["hw4mod8", "hwodd"])
+def test_label_targets_pix4_and_pix1_vs_fp64_oracle(H, W, bits):
+    """H W = 156 (= 4 mod 8) selects lc_label_targets_kernel<4>, H W = 143 (odd) <1> (launch_label_targets: PIX = 8 / 4 / 1, the widest
+    that divides H W with every buffer aligned for it).  xyz_gt, the continuous target or the Gray-coded / raw planes with the black
+    background inversion, against the fp64 oracle (quantiser near-ties excused as in test_annots_on_the_fly_vs_reference)."""
+    from lc_amd import floatbits, labels
+
+    assert floatbits._black_background
+    gen = torch.Generator().manual_seed(H * W + (0 if bits is None else 1))
+    hz, Rt, K, msk, sc, T = _label_inputs(gen, 3, H, W)
+    xyz, noc, tgt, raw = labels._targets(hz.to(DEV), Rt.to(DEV), K.to(DEV), msk=msk.to(DEV), noc_scale=sc.to(DEV), xform=T.to(DEV),
+                                         bit_cnt=None if bits is None else list(bits), want_targets=True)
+    rxyz, rnoc, rtgt, rraw, arg = O.targets(hz.double(), Rt.double(), K.double(), msk, sc.double(), T.double(), None if bits is None else list(bits))
+    assert ((xyz.cpu().double() - rxyz).abs().max() <= 1e-5 * rxyz.abs().max())
+    if bits is None:
+        assert ((noc.cpu().double() - rnoc).abs().max() <= 1e-5 * rnoc.abs().max())
+    else:
+        _check_bits(tgt, rtgt, arg)
+        _check_bits(raw, rraw, arg)
+
+
+@pytest.mark.parametrize("bits", [None, (7, 6, 5)], ids=["noc", "code"])
+@pytest.mark.parametrize("mask", ["u8", "f32"])
+def test_label_targets_forms_are_identical_on_the_same_pixels(bits, mask):
+    """H W = 160 (a multiple of 8): aligned buffers take lc_label_targets_kernel<8>; a byte mask at storage offset 4 only allows 4-pixel
+    accesses (<4>), a float mask at offset 4 floats keeps the 16-byte alignment (<8>), homo_z at an offset of one float defeats every vector
+    access (<1>).  Every output is bit-identical across the forms (the per-pixel arithmetic does not depend on PIX) and matches the oracle."""
+    from lc_amd import labels
+
+    gen = torch.Generator().manual_seed(160 + (0 if bits is None else 1))
+    hz, Rt, K, msk, sc, T = _label_inputs(gen, 2, 10, 16)
+    m = msk if mask == "u8" else msk.float()
+    kw = dict(noc_scale=sc.to(DEV), xform=T.to(DEV), bit_cnt=None if bits is None else list(bits), want_targets=True)
+    res = []
+    for hz_off, m_off in ((0, 0), (0, 4), (1, 0), (1, 4)):
+        mm = _at_offset(m.to(torch.uint8) if mask == "u8" else m, m_off)
+        res.append(labels._targets(_at_offset(hz, hz_off), Rt.to(DEV), K.to(DEV), msk=mm, **kw))
+    for r in res[1:]:
+        for a, c in zip(res[0], r):
+            assert (a is None) == (c is None) and (a is None or torch.equal(a, c))
+    rxyz, rnoc, rtgt, rraw, arg = O.targets(hz.double(), Rt.double(), K.double(), msk, sc.double(), T.double(), None if bits is None else list(bits))
+    xyz, noc, tgt, raw = res[0]
+    assert ((xyz.cpu().double() - rxyz).abs().max() <= 1e-5 * rxyz.abs().max())
+    if bits is None:
+        assert ((noc.cpu().double() - rnoc).abs().max() <= 1e-5 * rnoc.abs().max())
+    else:
+        _check_bits(tgt, rtgt, arg)
+        _check_bits(raw, rraw, arg)

@@ -235,3 +235,34 @@ def test_tiled_form_under_concurrency_and_replay():
         graph.replay()
     torch.cuda.synchronize()
     assert all(torch.equal(a, c) for a, c in zip(want[:4], got[:4]))
+
+
+@pytest.mark.parametrize("B,N,seed", [(2, 257, 20), (3, 1024, 21), (2, 1849, 22)])
+def test_cov2d_dense_forms_vs_oracle_and_each_other(B, N, seed):
+    """cov_2d (the covariance of the projected points) beyond N = 256: tiled=False forces the workgroup-per-sample loop
+    lc_cov_loss_kernel<false, true>; tiled=True takes lc_cov_loss_tiled_kernel<true> where the workspace query is positive (N = 1024 and
+    1849: 16 / 29 tiles, cut at least three ways) and the loop form at N = 257 (five tiles).  Both against the fp64 oracle with
+    cov_2d, and bit-identical to each other (lc_loss.hip: all forms add a sample's sums in tile order)."""
+    from lc_amd import _lib, synth
+    from lc_amd import cov_mixed as cm
+    from oracle import lc_loss_oracle as orc
+
+    dev = torch.device("cuda:0")
+    b = synth.make_batch(B, N, seed=200 + seed, outlier_frac=0.1)
+    g = torch.Generator().manual_seed(seed)
+    valid = (torch.rand(B, N, generator=g) > 0.2).float()
+    valid[:, :3] = 1
+    go = torch.rand(B, generator=g) + 0.5
+    assert (_lib.load().lc_cov_loss_workspace_bytes(B, N) > 0) == (N > 257)
+    d = {k: v.to(dev) for k, v in b.items()}
+    args = (d["K"], d["pose"], d["pts3d"], d["pts2d"], d["inv_std"], valid.to(dev), d["bbox_3d"])
+    one = cm.loss_cov_mixed_fused(*args, grad_out=go.to(dev), want_aux=True, cov_2d=True, tiled=False)
+    til = cm.loss_cov_mixed_fused(*args, grad_out=go.to(dev), want_aux=True, cov_2d=True, tiled=True)
+    for a, c in zip(one, til):
+        assert torch.isfinite(a).all() and torch.equal(a, c)
+    b64 = {k: v.double() for k, v in b.items()}
+    rl, ru, rs, rx = orc.loss_and_grads(b64["K"], b64["pose"], b64["pts3d"], b64["pts2d"], b64["inv_std"], valid.double(), b64["bbox_3d"],
+                                        grad_out=go.double(), want_pts3d=True, cov_2d=True)
+    loss, gu, gs, gx = (t.cpu() for t in one[:4])
+    assert ((loss.double() - rl).abs() / rl.abs().clamp_min(1)).max().item() <= 3e-5
+    assert rel_err(gu, ru) <= 3e-4 and rel_err(gs, rs) <= 3e-4 and rel_err(gx, rx) <= 3e-4

@@ -209,3 +209,35 @@ def test_split_selection_soak_over_random_shapes():
                 m = live if x.dim() == 2 else live[..., None].expand_as(x)
                 assert torch.equal(x[m], y[m]), (case, B, H, W, sample, mode, q)
     assert tried >= 20
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+@pytest.mark.parametrize("B,H,W,sample", [(6, 32, 32, 2), (24, 128, 128, 1)])
+def test_fp32_coordinates_next_to_16bit_logits_select_what_fp32_logits_select(B, H, W, sample, dtype):
+    """An fp32 coordinate map next to 16-bit weight / visibility logits: lc_dense_frontend_select_kernel<T, float, false> (256 candidates),
+    <T, float, true> (16384 candidates: more than the four per thread of the register cache) and, with a workspace, the several-workgroups
+    form lc_dense_frontend_select_split_kernel<T, float>.  Rows, weights, points, indices and counts bit for bit those of the all-fp32 call on
+    the up-cast logits (the reductions add the same values in the same order whatever the map type), in every mode."""
+    from lc_amd.dense import dense_front_end_select
+
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(B * H + W)
+    xyz = torch.randn(B, 3, H, W, generator=g).to(dev)
+    yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+    blob = (((yy - H / 2) / (0.3 * H)) ** 2 + ((xx - W / 2) / (0.25 * W)) ** 2 < 1).float()
+    wl = (torch.randn(B, 2, H, W, generator=g) * 1.5 + 4 * blob).to(dev, dtype)
+    vl = ((blob * 2 - 1) * 3 + torch.randn(B, 1, H, W, generator=g)).to(dev, dtype)
+    ws = (torch.rand(B, generator=g) + 0.5).to(dev)
+    ns = (torch.rand(B, 3, generator=g) + 0.5).to(dev)
+    for mode, q in (("quantile_in_mask", 0.2), ("quantile", 0.3), ("mask", 0.0)):
+        kw = dict(seg_thresh=0.5, sample=sample, quantile=q, min_count=6, seed=3)
+        want = dense_front_end_select(xyz, wl.float(), ws, ns, vl.float(), mode, split=False, **kw)
+        N = want[0].shape[1]
+        live = torch.arange(N, device=dev)[None, :] < want[3][:, None]
+        for split in (False, True):
+            got = dense_front_end_select(xyz, wl, ws, ns, vl, mode, split=split, **kw)
+            assert torch.equal(got[3], want[3]), (mode, split)
+            for name, x, y in zip(("pts2d", "weights", "pts3d", "", "index"), got, want):
+                if name:
+                    m = live if x.dim() == 2 else live[..., None].expand_as(x)
+                    assert torch.equal(x[m], y[m]), (mode, split, name)
