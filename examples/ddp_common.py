@@ -23,6 +23,8 @@ def add_args(ap):
     ap.add_argument("--seed-offset", type=int, default=0)
     ap.add_argument("--report-comm", action="store_true", help="per step and per rank: gradient all-reduce payload (bytes, buckets) and time, the "
                     "small all-reduces of the loss (NormClipper norms, code histogram), next to SURVEY.md section 5's xGMI estimates")
+    ap.add_argument("--optim", default="adam", choices=["adam", "ranger"], help="ranger: lc_amd.optim.Ranger, the fused step of the reference's "
+                    "optimizer, at configs/glmo.yaml's lr 2e-4 and weight decay 1e-4 (adam: torch.optim.Adam, lr 1e-4)")
     ap.add_argument("--dump", default=None, help="write losses, NormClipper states and the flattened parameters of every rank to <dump>.rank<r>.pt")
 
 
@@ -67,6 +69,14 @@ def freeze_bn(model):
     for m in model.modules():
         if isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
             m.eval()
+
+
+def make_optimizer(args, params):
+    if args.optim == "ranger":
+        from lc_amd.optim import Ranger
+
+        return Ranger(params, lr=2e-4, weight_decay=1e-4)
+    return torch.optim.Adam(params, lr=1e-4)
 
 
 def flat_params(model):

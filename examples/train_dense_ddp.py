@@ -138,7 +138,7 @@ def main():
         report.attach(net)
     if args.bn_eval:
         ddp_common.freeze_bn(model)
-    opt = torch.optim.Adam(model.parameters(), lr=1e-4)
+    opt = ddp_common.make_optimizer(args, model.parameters())
     amp = {"fp16": torch.float16, "bf16": torch.bfloat16, "fp32": None}[args.dtype]
     scaler = torch.amp.GradScaler("cuda", enabled=amp is torch.float16)
     times, losses, clip_states = [], [], []

@@ -115,7 +115,7 @@ def main():
         report.attach(net)
     if args.bn_eval:
         ddp_common.freeze_bn(model)
-    opt = torch.optim.Adam(model.parameters(), lr=1e-4)
+    opt = ddp_common.make_optimizer(args, model.parameters())
     times, losses, clip_states = [], [], []
     params_at_start = ddp_common.flat_params(model) if args.dump else None
     graphed = None

@@ -14,7 +14,9 @@ Call surface (mirrors the reference):
     lc_amd.metrics.compute_pose_errors   <- lib/utils/evaluate.py:333
     lc_amd.inference.solve_pnp           <- test.py:47-136
     lc_amd.graphs.GraphedLoss / inference.GraphedSolvePnP   hipGraph replay of the launch-bound steps
+    lc_amd.optim.Ranger                  <- lib/optim/ranger.py:29 (fused step, liblc_amd_optim.so; opt-in in the drop-in)
     lc_amd.dropin                        run the reference's train.py / test.py on all of the above without editing them
-Native code: lc_amd/csrc/*.hip -> lc_amd/_C/liblc_amd.so (C ABI in include/lc_amd.h).
+Native code: lc_amd/csrc/*.hip -> lc_amd/_C/liblc_amd.so (C ABI in include/lc_amd.h);
+lc_amd/csrc/optim/*.hip -> lc_amd/_C/liblc_amd_optim.so (include/lc_amd_optim.h).
 """
 __version__ = "0.1.0"

@@ -1,10 +1,16 @@
-"""Builds lc_amd/_C/liblc_amd.so from lc_amd/csrc/*.hip with hipcc for gfx950 (cross-compiles without a GPU)."""
+"""Builds the native libraries with hipcc for gfx950 (cross-compiles without a GPU):
+
+    lc_amd/_C/liblc_amd.so        from lc_amd/csrc/*.hip        (the hot-path C ABI, include/lc_amd.h)
+    lc_amd/_C/liblc_amd_optim.so  from lc_amd/csrc/optim/*.hip  (the fused optimizer step, include/lc_amd_optim.h)
+
+Every function takes the library it works on as a `Target` (default: the hot-path library)."""
 from __future__ import annotations
 
 import glob
 import os
 import shutil
 import subprocess
+from typing import NamedTuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
@@ -20,24 +26,36 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found (set HIPCC or install ROCm under /opt/rocm)")
 
 
-def sources():
-    return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+class Target(NamedTuple):
+    """One library: the directory of its sources (non-recursive globs), its public header, where it goes, and the marker in front of
+    the source hash it carries (compiled in as the macro named by the marker without its colon)."""
+    src_dir: str
+    header: str
+    so_path: str
+    hash_marker: bytes
 
 
-HASH_MARKER = b"LC_AMD_SRC_HASH:"  # the library carries the hash of its own sources (lc_capi.hip: lc_amd_source_hash)
+MAIN = Target(CSRC, "lc_amd.h", SO_PATH, b"LC_AMD_SRC_HASH:")  # the library carries the hash of its own sources (lc_capi.hip: lc_amd_source_hash)
+OPTIM = Target(os.path.join(CSRC, "optim"), "lc_amd_optim.h", os.path.join(OUT_DIR, "liblc_amd_optim.so"), b"LC_AMD_OPTIM_SRC_HASH:")
+TARGETS = (MAIN, OPTIM)
+HASH_MARKER = MAIN.hash_marker
 
 
-def _deps():
-    return sources() + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(os.path.dirname(PKG), "include", "lc_amd.h")]
+def sources(target: Target = MAIN):
+    return sorted(glob.glob(os.path.join(target.src_dir, "*.hip")))
 
 
-def source_hash() -> str:
+def _deps(target: Target = MAIN):
+    return sources(target) + sorted(glob.glob(os.path.join(target.src_dir, "*.h"))) + [os.path.join(os.path.dirname(PKG), "include", target.header)]
+
+
+def source_hash(target: Target = MAIN) -> str:
     """sha256 over the names and contents of every source the library is built from (mtimes do not survive the copy onto a
     GPU box; contents do)."""
     import hashlib
 
     h = hashlib.sha256()
-    for d in _deps():
+    for d in _deps(target):
         if os.path.exists(d):
             h.update(os.path.basename(d).encode())
             h.update(open(d, "rb").read())
@@ -46,24 +64,24 @@ def source_hash() -> str:
     return h.hexdigest()
 
 
-def embedded_hash(path: str = SO_PATH):
+def embedded_hash(path: str = SO_PATH, marker: bytes = HASH_MARKER):
     """The source hash a built library was compiled from, read from its bytes (no dlopen: a stale library must not get loaded
     just to be asked), or None for a file without the marker."""
     try:
         blob = open(path, "rb").read()
     except OSError:
         return None
-    i = blob.find(HASH_MARKER)
+    i = blob.find(marker)
     if i < 0:
         return None
-    j = i + len(HASH_MARKER)
+    j = i + len(marker)
     return blob[j:j + 64].decode("ascii", "replace")
 
 
-def is_stale() -> bool:
-    """True when liblc_amd.so is missing or was built from other source contents than the ones on disk now.  The hash lives INSIDE
+def is_stale(target: Target = MAIN) -> bool:
+    """True when the library is missing or was built from other source contents than the ones on disk now.  The hash lives INSIDE
     the library, so a copied library keeps it and there is no window in which library and hash disagree."""
-    return embedded_hash(SO_PATH) != source_hash()
+    return embedded_hash(target.so_path, target.hash_marker) != source_hash(target)
 
 
 def hipcc_available() -> bool:
@@ -74,19 +92,19 @@ def hipcc_available() -> bool:
         return False
 
 
-def _locked(fn):
+def _locked(fn, target: Target = MAIN):
     import fcntl
 
     os.makedirs(OUT_DIR, exist_ok=True)
-    with open(SO_PATH + ".lock", "w") as lock:  # one builder at a time (pytest-xdist workers, torchrun ranks, A/B scripts)
+    with open(target.so_path + ".lock", "w") as lock:  # one builder at a time (pytest-xdist workers, torchrun ranks, A/B scripts)
         fcntl.flock(lock, fcntl.LOCK_EX)
         return fn()
 
 
-def build(force: bool = False, verbose: bool = False) -> str:
-    if not force and not is_stale():
-        return SO_PATH
-    return _locked(lambda: SO_PATH if (not force and not is_stale()) else _compile(SO_PATH, [], verbose))
+def build(force: bool = False, verbose: bool = False, target: Target = MAIN) -> str:
+    if not force and not is_stale(target):
+        return target.so_path
+    return _locked(lambda: target.so_path if (not force and not is_stale(target)) else _compile(target.so_path, [], verbose, target), target)
 
 
 # Extra compiler flags of single translation units.  The latency builds of the one-wave pose kernels are scheduled for the shortest
@@ -115,24 +133,25 @@ PER_FILE_FLAGS = {
 COMMON_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-ffp-contract=on"]
 
 
-def _compile(out: str, flags, verbose: bool) -> str:
+def _compile(out: str, flags, verbose: bool, target: Target = MAIN) -> str:
     """One object per .hip source (in parallel; per-file flags from PER_FILE_FLAGS), then one link."""
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
 
-    hipcc, digest = _hipcc(), source_hash()
+    hipcc, digest = _hipcc(), source_hash(target)
+    macro = target.hash_marker.decode().rstrip(":")
     tmp = out + f".tmp{os.getpid()}"
     with tempfile.TemporaryDirectory(prefix="lc_amd_build_") as objdir:
         def one(src):
             obj = os.path.join(objdir, os.path.basename(src) + ".o")
-            cmd = [hipcc, *COMMON_FLAGS, f'-DLC_AMD_SRC_HASH="{digest}"', *flags, *PER_FILE_FLAGS.get(os.path.basename(src), []), "-c", src, "-o", obj]
+            cmd = [hipcc, *COMMON_FLAGS, f'-D{macro}="{digest}"', *flags, *PER_FILE_FLAGS.get(os.path.basename(src), []), "-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd))
             subprocess.check_call(cmd)
             return obj
 
         with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
-            objs = list(pool.map(one, sources()))
+            objs = list(pool.map(one, sources(target)))
         link = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-fvisibility=hidden", *objs, "-o", tmp]
         if verbose:
             print(" ".join(link))
@@ -173,4 +192,5 @@ def build_variant(name: str, flags, verbose: bool = False) -> str:
 
 
 if __name__ == "__main__":
-    print(build(force=True, verbose=True))
+    for t in TARGETS:
+        print(build(force=True, verbose=True, target=t))

@@ -17,19 +17,25 @@
 Opt-in (`install(native_labels=True)`, or `python -m lc_amd.dropin --native-labels train.py ...`): label preparation on the device --
     losses.annots_on_the_fly / selete_best_pose / xyz_from_homo_z, symmetry.select_pose_2d / select_pose_3d -> lc_amd.labels
 (`train.py:58,116` look the names up on the module at call time).  Without it the reference's own label preparation runs.
+
+Opt-in (`install(native_optim=True)`, or `--native-optim`, in either order with `--native-labels`): the fused optimizer step --
+    lib.optim.ranger.Ranger (and the name `utils.Ranger`, utils.py:10, when the reference's utils is already imported) -> lc_amd.optim.Ranger
+Without it the reference's own Ranger runs.
 """
 from __future__ import annotations
 
 import importlib
+import os
 import runpy
 import sys
 import types
 
 
-def install(patch_ptnet: bool = True, gpu_initialiser=None, native_labels: bool = False) -> dict:
+def install(patch_ptnet: bool = True, gpu_initialiser=None, native_labels: bool = False, native_optim: bool = False) -> dict:
     """gpu_initialiser: True = also register the RANSAC-P3P kernel as `lib.pnp.cv2_solver` (same `solve` surface,
     `test.py:59,120`); None (default) = only when OpenCV cannot be imported, so that `test.py` runs without it.
-    native_labels: also rebind the reference's label-preparation names to lc_amd.labels (done["labels"])."""
+    native_labels: also rebind the reference's label-preparation names to lc_amd.labels (done["labels"]).
+    native_optim: also rebind the reference's Ranger to lc_amd.optim.Ranger (done["optim"])."""
     from . import cov_mixed as cm
     from . import ptnet as head
     from .pnp import cer_solver, gpu_solver, pnp_ceres
@@ -103,6 +109,8 @@ def install(patch_ptnet: bool = True, gpu_initialiser=None, native_labels: bool 
             done["ptnet"] = False
     if native_labels:
         done["labels"] = _install_labels()
+    if native_optim:
+        done["optim"] = _install_optim()
     return done
 
 
@@ -122,18 +130,37 @@ def _install_labels() -> bool:
     return True
 
 
+def _install_optim() -> bool:
+    from . import optim
+
+    try:
+        ref = importlib.import_module("lib.optim.ranger")
+    except Exception:
+        return False
+    ref.Ranger = optim.Ranger
+    utils = sys.modules.get("utils")
+    if utils is not None and getattr(utils, "Ranger", None) is not None and getattr(utils, "__file__", None) and \
+            os.path.dirname(os.path.abspath(utils.__file__)) == os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(ref.__file__)))):
+        utils.Ranger = optim.Ranger  # `from lib.optim.ranger import Ranger` (utils.py:10) ran before the rebinding
+    return True
+
+
+_FLAGS = ("--native-labels", "--native-optim")
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    native_labels = bool(argv) and argv[0] == "--native-labels"
-    if native_labels:
-        argv = argv[1:]
+    flags = set()
+    while argv and argv[0] in _FLAGS:
+        flags.add(argv.pop(0))
+    native_labels, native_optim = "--native-labels" in flags, "--native-optim" in flags
     if not argv:
         raise SystemExit(__doc__)
     script = argv[0]
-    import os
-
     sys.path.insert(0, os.path.dirname(os.path.abspath(script)))
-    print("lc_amd.dropin:", install(native_labels=native_labels), file=sys.stderr)
+    # native_optim is passed only when asked for: without the flag install() gets exactly the arguments it got before the flag existed
+    kw = dict(native_labels=native_labels, **({"native_optim": True} if native_optim else {}))
+    print("lc_amd.dropin:", install(**kw), file=sys.stderr)
     sys.argv = argv
     runpy.run_path(script, run_name="__main__")
 
