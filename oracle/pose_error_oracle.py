@@ -15,15 +15,34 @@ def add(R_est, t_est, R_gt, t_gt, pts):
     return np.linalg.norm(transform(pts, R_est, t_est) - transform(pts, R_gt, t_gt), axis=1).mean()
 
 
-def adi(R_est, t_est, R_gt, t_gt, pts):
+def nearest(R_est, t_est, R_gt, t_gt, pts, k=1):
+    """Distances and indices of the k nearest est-pose vertices of every gt-pose vertex: (M,) for k = 1, (M, k) otherwise."""
     est, gt = transform(pts, R_est, t_est), transform(pts, R_gt, t_gt)
-    d, _ = spatial.cKDTree(est).query(gt, k=1)
+    return spatial.cKDTree(est).query(gt, k=k)
+
+
+def adi(R_est, t_est, R_gt, t_gt, pts):
+    d, _ = nearest(R_est, t_est, R_gt, t_gt, pts)
+    return d.mean()
+
+
+def adi_without_target(R_est, t_est, R_gt, t_gt, pts, j):
+    """ADI when est-pose vertex j is missing from the search (every gt-pose vertex is still a query)."""
+    est, gt = transform(pts, R_est, t_est), transform(pts, R_gt, t_gt)
+    d, _ = spatial.cKDTree(np.delete(est, j, axis=0)).query(gt, k=1)
     return d.mean()
 
 
 def re(R_est, R_gt):
     c = 0.5 * (np.trace(R_est @ np.linalg.inv(R_gt)) - 1.0)
     return math.degrees(math.acos(min(1.0, max(-1.0, float(c)))))
+
+
+def re_transposed(R_est, R_gt):
+    """`re` with R_gt^T in place of inv(R_gt): the same number for an orthonormal R_gt, and what lc_metrics.hip computes (the trace of
+    R_est R_gt^T is the sum of the nine products of equal entries)."""
+    c = 0.5 * (float(np.sum(R_est * R_gt)) - 1.0)
+    return math.degrees(math.acos(min(1.0, max(-1.0, c))))
 
 
 def te(t_est, t_gt):

@@ -63,7 +63,14 @@ FORMS = [
                                                                         "test_gpu_head::test_head_64x64_forms_at_offset_views"]),
     # ---- lc_kpt.hip / lc_metrics.hip ------------------------------------------------------------------------------------------
     (r"lc_kpt_nll_kernel", ["test_gpu_kpt::test_kpt_nll_vs_oracle"]),
-    (r"lc_pose_errors_kernel", ["test_gpu_metrics::test_pose_errors_vs_reference_golden"]),
+    # one form; the tests after the first walk the paths inside it (tile, pair-slot and query-group edges, offsets, want_adi, the scalars)
+    (r"lc_pose_errors_kernel", ["test_gpu_metrics::test_pose_errors_vs_reference_golden", "test_gpu_metrics::test_pose_errors_packed_objects_and_large_cloud",
+                                "test_gpu_metrics::test_witness_clouds_in_one_packed_launch",
+                                "test_gpu_metrics::test_packed_poses_equal_their_own_launches_and_repeat_bit_for_bit",
+                                "test_gpu_metrics::test_symmetric_object_adi_finds_another_vertex", "test_gpu_metrics::test_large_random_rotation_errors",
+                                "test_gpu_metrics::test_identical_poses_give_exact_zeros", "test_gpu_metrics::test_without_adi_the_other_outputs_keep_their_bits",
+                                "test_gpu_metrics::test_rotation_error_to_the_last_float32_digit", "test_gpu_metrics::test_translations_as_columns",
+                                "test_gpu_metrics::test_pose_errors_from_states_with_quaternions_of_any_length"]),
     # ---- lc_labels.hip: on-device label preparation ----------------------------------------------------------------------------
     (r"lc_sym_select_kernelILi(?:1|4)ELi512E", ["test_gpu_labels::test_selection_sweep_vs_fp64_oracle"]),
     (r"lc_sym_select_kernelILi16ELi256E", ["test_gpu_labels::test_selection_sweep_vs_fp64_oracle"]),
