@@ -2,6 +2,7 @@
 
     lc_amd/_C/liblc_amd.so        from lc_amd/csrc/*.hip        (the hot-path C ABI, include/lc_amd.h)
     lc_amd/_C/liblc_amd_optim.so  from lc_amd/csrc/optim/*.hip  (the fused optimizer step, include/lc_amd_optim.h)
+    lc_amd/_C/liblc_amd_posecov.so  from lc_amd/csrc/posecov/*.hip  (the test-time pose covariance, include/lc_amd_posecov.h)
 
 Every function takes the library it works on as a `Target` (default: the hot-path library)."""
 from __future__ import annotations
@@ -37,7 +38,8 @@ class Target(NamedTuple):
 
 MAIN = Target(CSRC, "lc_amd.h", SO_PATH, b"LC_AMD_SRC_HASH:")  # the library carries the hash of its own sources (lc_capi.hip: lc_amd_source_hash)
 OPTIM = Target(os.path.join(CSRC, "optim"), "lc_amd_optim.h", os.path.join(OUT_DIR, "liblc_amd_optim.so"), b"LC_AMD_OPTIM_SRC_HASH:")
-TARGETS = (MAIN, OPTIM)
+POSECOV = Target(os.path.join(CSRC, "posecov"), "lc_amd_posecov.h", os.path.join(OUT_DIR, "liblc_amd_posecov.so"), b"LC_AMD_POSECOV_SRC_HASH:")
+TARGETS = (MAIN, OPTIM, POSECOV)
 HASH_MARKER = MAIN.hash_marker
 
 

@@ -11,6 +11,9 @@ The reference walks Python lists here (one `nonzero()` = one device sync per sam
 re-batching, a multiprocessing pool around OpenCV); this module keeps one padded batch and an int32 `counts` vector on the
 device from the first kernel to the last.  The returned dict has the reference's keys ('weighted', 'ransac',
 'weighted-filtered'), each a (B,7) tensor of `w,x,y,z,tx,ty,tz`.
+
+`solve_pnp_with_cov` returns the same states and, for every weighted solver, the covariance of its pose and the predicted box-corner
+error (`lc_amd.posecov.PoseCov`): one more launch behind the solve, on the selection and weights that solver solved.
 """
 from __future__ import annotations
 
@@ -24,6 +27,7 @@ from . import floatbits, splitws
 from .dense import FUSED_SELECT_MAX_POINTS, dense_front_end_select, dense_front_end_with_visibility, dense_select
 from .losses import nn_out_to_xyz
 from .pnp import gpu_solver, pnp_ceres
+from .posecov import PoseCov, pose_covariance
 
 
 def quantile_msk(den_inv_std2d: Tensor, quantile) -> Tensor:
@@ -68,6 +72,28 @@ def solve_pnp(cfg, out_dict, gt_dict):
     return {"weighted": weighted, "ransac": start}
 
 
+def _cov_kwargs(cfg, gt_dict):
+    """What `pose_covariance` needs beyond the solver's inputs: the object's box corners (required), its diameter (optional, 3D only)."""
+    if "bbox_3d" not in gt_dict:
+        raise KeyError("solve_pnp_with_cov needs gt_dict['bbox_3d'] ((B,8,3) box corners in the object frame): the reference's test blob does "
+                       "not carry it, add it from the object's model info")
+    cov_2d = bool(cfg.get("cov_2d", False))
+    return dict(bbox_3d=gt_dict["bbox_3d"], diameter=None if cov_2d else gt_dict.get("diameter", None), cov_2d=cov_2d)
+
+
+@torch.no_grad()
+def solve_pnp_with_cov(cfg, out_dict, gt_dict):
+    """-> (states, covs): `states` is what `solve_pnp` returns; `covs` maps each weighted solver in it ('weighted', 'weighted-filtered';
+    never 'ransac') to the `PoseCov` of its pose, evaluated on the correspondences, weights and load-time filters that solver solved."""
+    ckw = _cov_kwargs(cfg, gt_dict)
+    if "pts2d" not in out_dict:
+        return solve_pnp_dense(cfg, out_dict, gt_dict, with_cov=True)
+    states = solve_pnp(cfg, out_dict, gt_dict)
+    cov = pose_covariance(gt_dict["out_K"], gt_dict["pts3d"], out_dict["pts2d"], out_dict["pts2d_std"], states["weighted"], nan_to_num=True,
+                          weights_are_std=True, **ckw)
+    return states, {"weighted": cov}
+
+
 _SIDE_STREAMS = {}  # device index -> streams the sub-batches of a wide test-time batch run on
 
 
@@ -88,13 +114,13 @@ def _sub_batch_count(B: int, N: int) -> int:
 
 
 @torch.no_grad()
-def solve_pnp_dense(cfg, out_dict, gt_dict):
-    """Dense heads (`test.py:67-136`)."""
+def solve_pnp_dense(cfg, out_dict, gt_dict, with_cov: bool = False):
+    """Dense heads (`test.py:67-136`).  with_cov: -> (states, covs) as `solve_pnp_with_cov` returns them."""
     B, _, H, W = out_dict["xyz_weight_logits"].shape
     stride = cfg.get("dense_sample", 2)
     parts = _sub_batch_count(B, -(-H // stride) * -(-W // stride))
     if parts <= 1:
-        return _solve_pnp_dense(cfg, out_dict, gt_dict, 0)
+        return _solve_pnp_dense(cfg, out_dict, gt_dict, 0, with_cov)
     dev = out_dict["xyz_weight_logits"].device
     cur = torch.cuda.current_stream(dev)
     pool = _SIDE_STREAMS.setdefault(dev.index if dev.index is not None else torch.cuda.current_device(), [])
@@ -106,16 +132,22 @@ def solve_pnp_dense(cfg, out_dict, gt_dict):
     for (b0, b1), side in zip(bounds, pool):
         side.wait_stream(cur)  # the network's outputs are ready on the caller's stream
         with torch.cuda.stream(side), splitws.no_split():  # concurrent launches: forms whose workgroups wait for each other would stay correct (rescue launch) but crawl
-            results.append(_solve_pnp_dense(cfg, cut(out_dict, b0, b1), cut(gt_dict, b0, b1), b0))
+            results.append(_solve_pnp_dense(cfg, cut(out_dict, b0, b1), cut(gt_dict, b0, b1), b0, with_cov))
     for side in pool[:parts]:
         cur.wait_stream(side)
-    for res in results:  # allocated on the side streams, read from here on by the caller's
-        for t in res.values():
+    covs = [res[1] for res in results] if with_cov else []
+    results = [res[0] for res in results] if with_cov else results
+    for res in results + [c for d in covs for c in d.values()]:  # allocated on the side streams, read from here on by the caller's
+        for t in (res.values() if isinstance(res, dict) else res):
             t.record_stream(cur)
-    return {k: torch.cat([res[k] for res in results]) for k in results[0]}
+    states = {k: torch.cat([res[k] for res in results]) for k in results[0]}
+    if not with_cov:
+        return states
+    return states, {k: PoseCov(*(torch.cat(f) for f in zip(*(d[k] for d in covs)))) for k in covs[0]}
 
 
-def _solve_pnp_dense(cfg, out_dict, gt_dict, pose0):
+def _solve_pnp_dense(cfg, out_dict, gt_dict, pose0, with_cov=False):
+    ckw = _cov_kwargs(cfg, gt_dict) if with_cov else None
     K = gt_dict["out_K"]
     stride = cfg.get("dense_sample", 2)
     thr = cfg.get("seg_thresh", 0.5)
@@ -187,18 +219,35 @@ def _solve_pnp_dense(cfg, out_dict, gt_dict, pose0):
         (start, _, _), (states, _, _) = pnp_ceres.solve_chain_device(
             refine, dict(cam_mat=K, pts3d=X2, pts2d=U2, sqrtL=W2, n_points=C2, shared_poses=B, **weighted))
         out["weighted"], out["weighted-filtered"] = states.chunk(2)
+        cov_of = dict(rows=(X2, U2, W2, states, C2), shared_poses=B)  # ONE covariance launch for both selections too
     elif "weighted_filtered" in wanted:
         fu, ficov, fx, fcounts, _ = filtered["result"]
         (start, _, _), (out["weighted-filtered"], _, _) = pnp_ceres.solve_chain_device(
             refine, dict(cam_mat=K, pts3d=fx, pts2d=fu, sqrtL=ficov, n_points=fcounts, **weighted))
+        cov_of = dict(rows=(fx, fu, ficov, out["weighted-filtered"], fcounts), key="weighted-filtered")
     elif "weighted" in wanted:
         (start, _, _), (out["weighted"], _, _) = pnp_ceres.solve_chain_device(
             refine, dict(cam_mat=K, pts3d=x, pts2d=u, sqrtL=icov, n_points=counts, **weighted))
+        cov_of = dict(rows=(x, u, icov, out["weighted"], counts), key="weighted")
     else:
         start = pnp_ceres.solve_device(**refine)[0]
+        cov_of = None
     if "ransac" in wanted:
         out["ransac"] = start
-    return {k: out[k] for k in ("ransac", "weighted-filtered", "weighted") if k in out}  # key order of test.py:129-135
+    states = {k: out[k] for k in ("ransac", "weighted-filtered", "weighted") if k in out}  # key order of test.py:129-135
+    if not with_cov:
+        return states
+    # the covariance of each weighted pose: its own launch behind the solve, with the solve's inputs and load-time filters
+    covs = {}
+    if cov_of is not None:
+        cx, cu, cw, cpose, ccounts = cov_of["rows"]
+        pc = pose_covariance(K, cx, cu, cw, cpose, ccounts, nan_to_num=True, shared_poses=cov_of.get("shared_poses"), **ckw)
+        if "key" in cov_of:
+            covs[cov_of["key"]] = pc
+        else:
+            first, second = zip(*(f.chunk(2) for f in pc))
+            covs["weighted"], covs["weighted-filtered"] = PoseCov(*first), PoseCov(*second)
+    return states, {k: covs[k] for k in ("weighted-filtered", "weighted") if k in covs}
 
 
 @contextlib.contextmanager
@@ -224,10 +273,15 @@ class GraphedSolvePnP:
         poses = solver(out_dict, gt_dict)                     # copies the tensors into the static buffers, replays
 
     Every tensor entry of the two dicts is treated as an input; non-tensor entries (bit counts, ...) are frozen at capture.
+    with_cov=True captures `solve_pnp_with_cov` instead (the covariance launches ride in the same graph) and returns (states, covs).
     """
 
-    def __init__(self, cfg, out_dict, gt_dict, warmup: int = 2):
+    def __init__(self, cfg, out_dict, gt_dict, warmup: int = 2, with_cov: bool = False):
         self.cfg = cfg
+        self.with_cov = with_cov
+        solve = solve_pnp_with_cov if with_cov else solve_pnp
+        if with_cov:
+            _cov_kwargs(cfg, gt_dict)  # a missing bbox_3d raises before anything is allocated
         # static input buffers, contiguous whatever the example's layout: a strided network output would otherwise be copied into
         # shape by a torch launch INSIDE every replay
         own = lambda v: v.detach().clone(memory_format=torch.contiguous_format) if isinstance(v, Tensor) else v  # noqa: E731
@@ -240,7 +294,7 @@ class GraphedSolvePnP:
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):  # warm-up off the capture: module loading, allocator pools, LDS attributes
             for _ in range(max(1, warmup)):
-                solve_pnp(cfg, self._out, self._gt)
+                solve(cfg, self._out, self._gt)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
@@ -248,7 +302,7 @@ class GraphedSolvePnP:
         self._split_ws = (torch.zeros(splitws.max_bytes("pnp", dev), device=dev, dtype=torch.uint8), torch.zeros(splitws.max_bytes("select", dev), device=dev, dtype=torch.uint8))
         torch.cuda.synchronize(dev)
         with quiet_capture(), torch.cuda.graph(self.graph), splitws.owned(pnp=self._split_ws[0], select=self._split_ws[1]):
-            self._res = solve_pnp(cfg, self._out, self._gt)
+            self._res = solve(cfg, self._out, self._gt)
 
     @torch.no_grad()
     def __call__(self, out_dict, gt_dict):
@@ -261,4 +315,7 @@ class GraphedSolvePnP:
                     if src.data_ptr() != buf.data_ptr():
                         buf.copy_(src, non_blocking=True)
         self.graph.replay()
-        return {k: v.clone() for k, v in self._res.items()}
+        if not self.with_cov:
+            return {k: v.clone() for k, v in self._res.items()}
+        states, covs = self._res
+        return {k: v.clone() for k, v in states.items()}, {k: PoseCov(*(f.clone() for f in c)) for k, c in covs.items()}
