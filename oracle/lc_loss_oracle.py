@@ -194,7 +194,7 @@ def loss_cov_mixed(K: Tensor, pose: Tensor, pts3d: Tensor, pts2d: Tensor, inv_st
     lin = torch.linalg.vector_norm(dlt.reshape(dlt.shape[:-1] + (8, gdim)), dim=-1).mean(-1)
     loss = prior_error.log() + 0.5 * (cov_err + lin) / prior_error
     if return_intermediates:
-        return loss, dict(w=w, c=c, Hinv=S, A=A, G=G, e=e, info=info,
+        return loss, dict(w=w, c=c, Hinv=S, A=A, G=G, e=e, info=info, err=err, mean_abs=mean_abs, d_s=d_s,
                           prior_error=prior_error, cov_err=cov_err, linear_err=lin)
     return loss
 

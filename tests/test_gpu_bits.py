@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import rowwise as rw
 from tests.util import golden_files, case_name, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -23,6 +24,11 @@ def test_bits_decode_vs_reference(path):
     (gl,) = torch.autograd.grad(out, lg, torch.from_numpy(z["in_ct"]).to(dev))
     assert rel_err(out.detach().cpu(), z["f64_noc_gt"]) <= 2e-6
     assert rel_err(gl.cpu(), z["f64_g_logits"]) <= 5e-6
+    # per sample and coordinate (tests/rowwise.py): the channels of one coordinate's bits are a row; the same 5e-6 against the row's own largest
+    # entry, the reference's fp32 run setting the bound where it exceeds that on a row
+    for c, (lo, n) in enumerate(zip(np.cumsum([0] + bits[:-1]), bits)):
+        cut = lambda t: torch.as_tensor(t)[:, lo:lo + n]  # noqa: E731
+        rw.check_kept(f"bits g_logits coordinate {c}", cut(gl.cpu()), cut(z["f64_g_logits"]), cut(z["f32_g_logits"]), 5e-6)
     inf = fb.nn_logits2noc(lg.detach(), bits)
     assert rel_err(inf.cpu(), z["f64_noc_inf"]) <= 2e-6
 

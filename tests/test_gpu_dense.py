@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import rowwise as rw
 from tests.util import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -33,6 +34,13 @@ def test_dense_front_end_vs_oracle(B, H, W, sample, tl):
     go = torch.autograd.grad([r, q3], l64, [cs.double(), c3.double()])
     for a, b_ in zip(gk, go):
         assert rel_err(a.cpu(), b_) <= 5e-6
+    # sample by sample (tests/rowwise.py): the same 5e-6 against each sample's own largest entry, or twice the oracle's fp32 evaluation where
+    # that already exceeds 5e-6 on the sample
+    l32 = [t.clone().requires_grad_(True) for t in (xyz, wl, ws)]
+    _, r32, q32 = dense_oracle.dense_front_end(l32[0], l32[1], l32[2], ns, sample, tl)
+    g32 = torch.autograd.grad([r32, q32], l32, [cs, c3])
+    for name, a, b_, c_ in zip(("d_xyz", "d_w_logits", "d_w_scale"), gk, go, g32):
+        rw.check_kept(f"front end {B}x{H}x{W} {name} per sample", a, b_, c_, 5e-6)
 
 
 def test_dense_loss_fn_end_to_end_on_gpu():
@@ -242,6 +250,15 @@ def test_dense_aux_losses_equal_the_torch_formulas(B, H, W, with_xyz, with_w, ma
     for a, b in ((xg, x64), (sg, s64), (wg, w64)):
         if b is not None:
             assert (a.grad.cpu().double() - b.grad).abs().max() <= 2e-6 * b.grad.abs().max(), float((a.grad.cpu().double() - b.grad).abs().max())
+    # sample by sample (tests/rowwise.py): the same 2e-6 against each sample's own largest entry, or twice the float32 evaluation of the same
+    # torch formulas where that already exceeds 2e-6 on the sample
+    x32, s32, w32 = (None if t is None else t.clone().requires_grad_(True) for t in (xyz, seg, wl))
+    want32 = [F.l1_loss(x32 * msk[:, None], tgt) if with_xyz else None, seg_fn(s32, vis[:, None], reduction="mean"),
+              seg_fn(w32, vis[:, None].expand_as(w32), reduction="mean") if with_w else None]
+    sum(u * v for u, v in zip(up, want32) if v is not None).backward()
+    for name, a, b, c in (("d_xyz", xg, x64, x32), ("d_seg", sg, s64, s32), ("d_w_logits", wg, w64, w32)):
+        if b is not None:
+            rw.check_kept(f"aux {seg_type} {B}x{H}x{W} {name} per sample", a.grad, b.grad, c.grad, 2e-6)
 
 
 @pytest.mark.parametrize("B,C,H,W", [(32, 17, 64, 64), (3, 21, 37, 29), (2, 72, 16, 16), (4, 5, 128, 128), (32, 21, 128, 128), (5, 7, 6, 6), (3, 4, 40, 36)])
@@ -254,7 +271,7 @@ def test_xyz_bin_loss_equals_the_torch_formulas(B, C, H, W):
 
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(C * H)
-    fused, plain = Loss_xyz_bin(C).to(dev), Loss_xyz_bin(C).double()
+    fused, plain, plain32 = Loss_xyz_bin(C).to(dev), Loss_xyz_bin(C).double(), Loss_xyz_bin(C)  # (float32 on the CPU: the same torch formulas)
     for step in range(3):
         logits = torch.randn(B, C, H, W, generator=g) * 3
         logits[0, 0, 0, :3] = torch.tensor([0.0, 50.0, -50.0])[:min(3, W)]
@@ -268,6 +285,10 @@ def test_xyz_bin_loss_equals_the_torch_formulas(B, C, H, W):
         assert abs(float(la) - float(lb)) <= 2e-6 * max(1.0, abs(float(lb))), (step, float(la), float(lb))
         assert (fused.histogram.cpu().double() - plain.histogram).abs().max() <= 1e-6
         assert (a.grad.cpu().double() - b.grad).abs().max() <= 2e-6 * b.grad.abs().max()
+        # sample by sample (tests/rowwise.py): the same 2e-6 against the sample's own largest entry, or twice the formulas' float32 evaluation
+        c = logits.clone().requires_grad_(True)
+        (plain32(c, bits, vis) * 1.7).backward()
+        rw.check_kept(f"xyz_bin {B}x{C}x{H}x{W} step {step} d_logits per sample", a.grad, b.grad, c.grad, 2e-6)
     assert float((fused.histogram - 0.5).abs().max()) > 1e-3  # the EMA moved
 
 
@@ -280,7 +301,7 @@ def test_xyz_bin_loss_with_an_empty_and_a_full_visibility_mask(vis_sign):
     dev = torch.device("cuda:0")
     B, C, H, W = 3, 9, 24, 40
     g = torch.Generator().manual_seed(7)
-    fused, plain = Loss_xyz_bin(C).to(dev), Loss_xyz_bin(C).double()
+    fused, plain, plain32 = Loss_xyz_bin(C).to(dev), Loss_xyz_bin(C).double(), Loss_xyz_bin(C)  # (float32 on the CPU: the same torch formulas)
     for step in range(2):
         logits = torch.randn(B, C, H, W, generator=g) * 3
         bits = torch.rand(B, C, H, W, generator=g) < 0.5

@@ -107,6 +107,23 @@ def test_pose_unit_vs_oracle_and_reference_golden():
     ref = torch.from_numpy(z["f64_loss"]).double()
     assert ((unit.loss.cpu().double() - ref).abs() / ref.abs().clamp_min(1)).max().item() <= 3e-5
     assert rel_err(unit.d_pts2d.cpu(), z["f64_g_pts2d"]) <= 3e-4 and rel_err(unit.d_inv_std.cpu(), z["f64_g_inv_std"]) <= 3e-4
+    # (a') point by point (tests/rowwise.py), the bound from the fixture's own fp32 run.  The fixture's f64 run read the unrounded fp64 inputs
+    # and its f32 run the fp32 ones the unit reads, so against f64_g_* every point carries the effect of rounding the inputs (up to 3.3e-4 of a
+    # point's d_pts2d and 7.1e-3 of its d_inv_std for an exact evaluation, the oracle on the CPU) and only the fp32 run's worst point bounds it;
+    # against the fp64 oracle on the identical fp32 inputs each point is held to max(2 x the f32 run's distance at that point, 4 x 2^-24).
+    from tests import rowwise as rw
+    from tests.test_gpu_loss import oracle_run
+
+    keys = ("loss", "g_pts2d", "g_inv_std", "g_pts3d")
+    o64, o32 = (dict(zip(keys, oracle_run(ins, dt, True, **kwargs))) for dt in (torch.float64, torch.float32))
+    for k, g in (("g_pts2d", unit.d_pts2d.cpu()), ("g_inv_std", unit.d_inv_std.cpu())):
+        f32, f64 = torch.from_numpy(z["f32_" + k]), torch.from_numpy(z["f64_" + k])
+        worst = rw.bound_from_reference(rw.point_error(f32, f64).max().item())
+        rw.check(f"pose unit {k} per point vs the fixture's f64 run", g, f64, f32, point_dims=1, bound=worst)
+        rw.check(f"pose unit {k} per point vs the oracle on the same inputs", g, o64[k], f32, point_dims=1)
+    # (the fixture stores no d_pts3d: the oracle in fp32 stands in for the reference's fp32 run)
+    rw.check("pose unit g_pts3d per point vs the oracle on the same inputs", unit.d_pts3d.cpu(), o64["g_pts3d"], o32["g_pts3d"], point_dims=1)
+    rw.check("pose unit loss per sample", unit.loss.cpu()[:, None], o64["loss"][:, None], torch.from_numpy(z["f32_loss"])[:, None])
     # (b) the PnP half against the oracle on the same correspondences
     so, tro, reto = pnp_oracle.solve_batched(ins["start"].numpy(), ins["K"].numpy(), ins["pts2d"].numpy(), ins["pts3d"].numpy(),
                                              torch.diag_embed(ins["inv_std"]).numpy(), num_threads=4)

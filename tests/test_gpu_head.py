@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import rowwise as rw
 from tests.util import golden_files, case_name, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -24,6 +25,10 @@ def test_head_vs_golden(path):
     assert (std.detach().cpu().double() - torch.from_numpy(z["f64_std"])).abs().max().item() <= 2e-4
     assert rel_err(gl.cpu(), z["f64_g_logits"]) <= 2e-4
     assert rel_err(gl.cpu(), z["f32_g_logits"]) <= 2e-4
+    # map by map (tests/rowwise.py): the same 2e-4 against each map's own largest gradient entry, the reference's fp32 run setting the bound
+    # where it exceeds that on a map
+    maps = (-1,) + tuple(lg.shape[-2:])
+    rw.check_kept("head g_logits per map", gl, z["f64_g_logits"], z["f32_g_logits"], 2e-4, rows=maps)
     # the function on its own (probabilities in), ptnet.py:100-115
     pr = torch.from_numpy(z["f32_prob"]).to(dev).requires_grad_(True)
     m2, s2 = softargmax_2d_std(pr)
@@ -52,6 +57,9 @@ def test_head_odd_shapes_vs_torch(shape):
     assert (mean.detach().cpu().double() - m64.detach()).abs().max().item() <= 3e-4
     assert (std.detach().cpu().double() - s64.detach()).abs().max().item() <= 3e-4
     assert rel_err(gl.cpu(), g64) <= 3e-4
+    x32 = lg.clone().requires_grad_(True)
+    (g32,) = torch.autograd.grad(orc(x32), [x32], [ctm, cts])
+    rw.check_kept(f"head {shape} g_logits per map", gl, g64, g32, 3e-4, rows=(-1,) + shape[-2:])
 
 
 def test_head_full_size_properties():
@@ -169,11 +177,11 @@ HEAD_FORMS = {
 
 @pytest.mark.parametrize("prob", [False, True], ids=["logits", "prob"])
 @pytest.mark.parametrize("nv,vec", sorted(HEAD_FORMS), ids=[f"NV{n}_VEC{v}" for n, v in sorted(HEAD_FORMS)])
-def test_head_fwd_forms_fp32_vs_fp64(nv, vec, prob):
+def test_head_fwd_forms_fp32_vs_fp64(nv, vec, prob, spread=False):
     """Every (NV, VEC) form of the generic single-pass forward on fp32 maps, logits and probabilities in, forward and backward against
     the float64 restatement (oracle/softargmax_oracle.py).  The backward forms these shapes reach: lc_head_bwd_kernel<float, 4, false>
     (W % 4 == 0; none of these widths divides 1024, so the column-fixed form is not taken) and <float, 1, false> (W % 4 != 0 or a misaligned
-    map)."""
+    map).  The gradient is also judged map by map (tests/rowwise.py); `spread` (the test below) scales each map's cotangents by 10^U(-2, 2)."""
     from oracle import softargmax_oracle as orc
 
     H, W, off = HEAD_FORMS[(nv, vec)]
@@ -182,13 +190,32 @@ def test_head_fwd_forms_fp32_vs_fp64(nv, vec, prob):
     lg = torch.randn(2, 3, H, W, generator=g) * 3
     vals = lg.flatten(-2).softmax(-1).reshape(lg.shape) if prob else lg
     ct_m, ct_s = torch.randn(2, 3, 2, generator=g), torch.randn(2, 3, 2, generator=g)
+    if spread:
+        scale = 10 ** (torch.rand(2, 3, 1, generator=g) * 4 - 2)
+        ct_m, ct_s = ct_m * scale, ct_s * scale
     mean, std, gx = _head_fwd_bwd(_map_at(vals, torch.float32, off), prob, ct_m.to("cuda:0"), ct_s.to("cuda:0"))
+    fn = orc.softargmax_2d_std if prob else orc.spatial_softargmax_2d_std
     v64 = vals.double().requires_grad_(True)
-    m64, s64 = (orc.softargmax_2d_std if prob else orc.spatial_softargmax_2d_std)(v64)
+    m64, s64 = fn(v64)
     (g64,) = torch.autograd.grad((m64 * ct_m.double()).sum() + (s64 * ct_s.double()).sum(), v64)
     assert (mean.cpu().double() - m64.detach()).abs().max().item() <= 3e-4
     assert (std.cpu().double() - s64.detach()).abs().max().item() <= 3e-4
     assert rel_err(gx.cpu(), g64) <= 3e-4
+    v32 = vals.clone().requires_grad_(True)
+    m32, s32 = fn(v32)
+    (g32,) = torch.autograd.grad((m32 * ct_m).sum() + (s32 * ct_s).sum(), v32)
+    if spread:
+        big = g64.abs().flatten(-2).amax(-1).flatten()
+        assert big.max() / big.min() >= 100  # the maps' gradients differ in size by two decades and more
+    rw.check_kept(f"head NV{nv} VEC{vec} {'prob' if prob else 'logits'} gradient per map", gx, g64, g32, 3e-4, rows=(-1, H, W))
+
+
+@pytest.mark.parametrize("prob", [False, True], ids=["logits", "prob"])
+@pytest.mark.parametrize("nv,vec", sorted(HEAD_FORMS), ids=[f"NV{n}_VEC{v}" for n, v in sorted(HEAD_FORMS)])
+def test_head_fwd_forms_fp32_vs_fp64_with_cotangents_spread_over_four_decades(nv, vec, prob):
+    """The same forms and maps with each map's cotangents scaled by 10^U(-2, 2): maps with small gradients sit in the same launch as maps
+    with large ones, and each is judged against its own largest entry."""
+    test_head_fwd_forms_fp32_vs_fp64(nv, vec, prob, spread=True)
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])

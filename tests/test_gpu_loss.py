@@ -8,10 +8,74 @@ import numpy as np
 import pytest
 import torch
 
+from tests import rowwise as rw
 from tests.util import golden_files, case_name, load_loss_case, rel_err
 
 pytestmark = pytest.mark.gpu
 FILES = golden_files("lc_loss_")
+
+# ROW-WISE TOLERANCE (tests/rowwise.py; every `_rowwise` call below): each point's gradient against the fp64 oracle on the identical inputs,
+# max|kernel - fp64| over the point / max(the point's largest |fp64| entry, 1e-3 x its sample's largest), must not exceed
+# max(2 x the same measure of the fp32 reference at that point, 4 x 2^-24); the loss and H^-1 likewise per sample.  The fp32 reference is the
+# unmodified reference's own fp32 run where a fixture stores it (`f32_*`: it ran on these very fp32 inputs) and the oracle evaluated in
+# torch.float32 elsewhere.  The kernel's own output never enters a bound.
+SHAPES = [(1, 3, 0), (7, 5, 1), (3, 64, 2), (2, 65, 3), (2, 200, 4), (3, 255, 8), (16, 256, 9), (2, 257, 5), (1, 1849, 6), (33, 100, 7)]
+COV2D_SHAPES = [(2, 257, 20), (3, 1024, 21), (2, 1849, 22)]
+OUTLIER_SHAPES = [(8, 64, 30), (4, 1024, 31)]
+CENSUS_MIN_POINTS = 64  # below this a sample has too few points for a stable share of small gradients (1 x 3 and 7 x 5 stay as edge shapes)
+
+
+def fixture_has_fp32_reference(path):
+    """False for the noise-free fixture: its fp64 gradients are exact zeros where its fp32 run is round-off noise (tests/test_rowwise.py)."""
+    return "noisefree" not in path
+
+
+def shape_inputs(B, N, seed, batch_seed=None, outlier_frac=0.05):
+    """CPU inputs of the shape tests: synth.make_batch, a seeded valid mask (about a fifth of the points out) and the narrow cotangent
+    `rand + 0.5` every loss test has used so far."""
+    from lc_amd import synth
+
+    b = synth.make_batch(B, N, seed=seed if batch_seed is None else batch_seed, outlier_frac=outlier_frac)
+    g = torch.Generator().manual_seed(seed)
+    valid = (torch.rand(B, N, generator=g) > 0.2).float()
+    valid[:, :3] = 1
+    go = torch.rand(B, generator=g) + 0.5
+    return dict(b, valid=valid, grad_out=go)
+
+
+def wide_grad_out(B, seed):
+    """A cotangent spread over six decades, 10^U(-3, 3): samples whose whole gradient is small sit in the same launch as large ones."""
+    return 10 ** (torch.rand(B, generator=torch.Generator().manual_seed(7000 + seed)) * 6 - 3)
+
+
+def oracle_run(ins, dtype, want3=True, **kwargs):
+    """(loss, du, ds, dx) of the oracle evaluated in `dtype` on the (fp32-representable) inputs."""
+    from oracle import lc_loss_oracle as orc
+
+    i = {k: v.to(dtype) for k, v in ins.items()}
+    return orc.loss_and_grads(i["K"], i["pose"], i["pts3d"], i["pts2d"], i["inv_std"], i.get("valid"), i["bbox_3d"], grad_out=i["grad_out"],
+                              want_pts3d=want3, **kwargs)
+
+
+def _rowwise(what, got, ref64, ref32, where=None, samples=False, floor_only=False):
+    """got / ref64 / ref32: (loss, du, ds, dx); dx may be None.  Gradients point by point, with `samples` also sample by sample; the loss
+    per sample.  floor_only: the fp32 reference has no stable value (noise-free fixture), only 4 x 2^-24 is allowed."""
+    for name, g, r64, r32 in zip(("du", "ds", "dx"), got[1:], ref64[1:], ref32[1:]):
+        if r64 is None:
+            continue
+        g, r64, r32 = g.cpu(), r64.cpu(), (r64.cpu() if floor_only else r32.cpu())
+        rw.check(f"{what} {name} per point", g, r64, r32, point_dims=1, where=where)
+        if samples:
+            rw.check(f"{what} {name} per sample", g, r64, r32)
+    if where is None:
+        r32l = ref64[0] if floor_only else ref32[0]
+        rw.check(f"{what} loss per sample", got[0].cpu()[:, None], ref64[0].cpu()[:, None], r32l.cpu()[:, None])
+
+
+def census(ref_du):
+    """The condition that makes a point-wise check say more than `rel_err`: the share of points whose d_pts2d is below 1 % of the batch's
+    largest entry."""
+    return (rw.batch_share(ref_du) < 1e-2).double().mean().item()
 
 
 def _run(ins, kwargs, want3, use_autograd=True):
@@ -46,6 +110,10 @@ def test_loss_kernel_vs_golden(path, autograd):
     assert rel_err(gu, ru) <= 1e-4 and rel_err(gs, rs) <= 1e-4
     if want3:
         assert rel_err(gx, rx) <= 1e-4
+    # (1b) the same comparison row-wise, the bound from the reference's own fp32 run on these inputs.  The noise-free case has no such run to
+    # speak of (81 % of its fp64 gradient points are exact zeros that are noise in fp32, tests/test_rowwise.py): the floor alone is allowed.
+    f32 = tuple(None if (k == "g_pts3d" and not want3) else torch.from_numpy(z["f32_" + k]) for k in ("loss", "g_pts2d", "g_inv_std", "g_pts3d"))
+    _rowwise(case_name(path, "lc_loss_"), (loss, gu, gs, gx), (rl, ru, rs, rx), f32, floor_only=not fixture_has_fp32_reference(path))
     # (2) the reference's own outputs.  The noise-free case is excluded here: with err == 0 the fp64 reference sits on
     # exact zeros (c = w = 0 -> SPD fallback) that do not survive rounding the inputs to fp32, and the fp32 reference's
     # err is pure round-off noise -- there is no stable value to compare with (the oracle check above covers it).
@@ -60,28 +128,68 @@ def test_loss_kernel_vs_golden(path, autograd):
     if aux is not None and "f64_Hinv" in z.files and golden_tols:
         Hinv = aux[:, 4:].reshape(-1, 6, 6).double()
         assert rel_err(Hinv, z["f64_Hinv"]) <= 1e-4
+    if aux is not None and golden_tols:
+        # (the noise-free case stays out as above: its H is round-off noise, its inverse has no stable value)
+        # H^-1 per sample under the floor alone, against the oracle's H^-1 on the identical inputs.  The fixture's f64_Hinv was computed on the
+        # unrounded fp64 inputs: rounding the inputs to fp32 alone moves H^-1 by up to 4.4e-7 of a sample's largest entry (n3_B3_N3; 2.8e-7 on
+        # two samples of metric_B256_N64 -- the oracle in fp64 on both sets of inputs, on the CPU), which is above the floor and above twice
+        # the f32_Hinv's own distance on those samples.  The oracle on the identical inputs pins the same quantity without that term.
+        _, inter = orc.loss_cov_mixed(i64["K"], i64["pose"], i64["pts3d"], i64["pts2d"], i64["inv_std"], i64.get("valid"), bbox_3d=i64["bbox_3d"],
+                                      return_intermediates=True, **kwargs)
+        Hk, Ho = aux[:, 4:].reshape(-1, 6, 6), inter["Hinv"]
+        rw.check(case_name(path, "lc_loss_") + " Hinv per sample vs oracle", Hk, Ho, Ho, bound=rw.FLOOR)
 
 
-@pytest.mark.parametrize("B,N,seed", [(1, 3, 0), (7, 5, 1), (3, 64, 2), (2, 65, 3), (2, 200, 4), (3, 255, 8), (16, 256, 9), (2, 257, 5), (1, 1849, 6), (33, 100, 7)])
+@pytest.mark.parametrize("B,N,seed", SHAPES)
 def test_loss_kernel_vs_oracle_shapes(B, N, seed):
     """Ragged / odd sizes through both kernel variants (registers: N<=256, block-stride: N>256), with a valid mask.  255 / 256 / 257 sit on
     the switch between the two (`lc_loss.hip`: one workgroup with four points per lane up to N = 256, tiles beyond); B=16, N=256 is
-    BASELINE configs[0]'s loss shape (16 crops, 32x32 maps, stride 2)."""
-    from lc_amd import synth
-    from oracle import lc_loss_oracle as orc
-
-    b = synth.make_batch(B, N, seed=seed)
-    g = torch.Generator().manual_seed(seed)
-    valid = (torch.rand(B, N, generator=g) > 0.2).float()
-    valid[:, :3] = 1
-    go = torch.rand(B, generator=g) + 0.5
-    ins = dict(b, valid=valid, grad_out=go)
+    BASELINE configs[0]'s loss shape (16 crops, 32x32 maps, stride 2).  Row-wise (module comment) twice: with the narrow cotangent and with
+    one spread over six decades, then also sample by sample so that the small-cotangent samples are judged on their own."""
+    ins = shape_inputs(B, N, seed)
     loss, gu, gs, gx, _ = _run(ins, {}, True, True)
-    b64 = {k: v.double() for k, v in ins.items()}
-    rl, ru, rs, rx = orc.loss_and_grads(b64["K"], b64["pose"], b64["pts3d"], b64["pts2d"], b64["inv_std"], b64["valid"],
-                                        b64["bbox_3d"], grad_out=b64["grad_out"], want_pts3d=True)
+    rl, ru, rs, rx = oracle_run(ins, torch.float64)
     assert ((loss.double() - rl).abs() / rl.abs().clamp_min(1)).max().item() <= 3e-5
     assert rel_err(gu, ru) <= 3e-4 and rel_err(gs, rs) <= 3e-4 and rel_err(gx, rx) <= 3e-4
+    if N >= CENSUS_MIN_POINTS:
+        assert census(ru) >= 0.25
+    _rowwise(f"{B}x{N}", (loss, gu, gs, gx), (rl, ru, rs, rx), oracle_run(ins, torch.float32))
+    wide = dict(ins, grad_out=wide_grad_out(B, seed))
+    got = _run(wide, {}, True, True)[:4]
+    ref64 = oracle_run(wide, torch.float64)
+    if N >= CENSUS_MIN_POINTS:
+        assert census(ref64[1]) >= 0.25
+    _rowwise(f"{B}x{N} wide grad_out", got, ref64, oracle_run(wide, torch.float32), samples=True)
+
+
+@pytest.mark.parametrize("B,N,seed", OUTLIER_SHAPES)
+def test_loss_kernel_each_side_of_the_robust_thresholds(B, N, seed):
+    """30 % outliers (N(0, 20^2) px against N(0, 1)): the clamp of the error at max_err_len, the Huber knee of c at rel_thresh x the mean
+    |error| and the knee of the weight at d_s each split the points of the batch.  The sides are counted with the oracle, both must be
+    populated, and the row-wise check (module comment) is applied to each side by itself: a branch whose gradients are all small is not
+    hidden behind the one whose gradients are large.  A point is on the far side of a knee if either coordinate is; points masked out by
+    `valid` count on neither side.  N = 64 takes the one-workgroup form, N = 1024 the tiled one."""
+    from oracle import lc_loss_oracle as orc
+
+    ins = shape_inputs(B, N, seed, outlier_frac=0.3)
+    i64 = {k: v.double() for k, v in ins.items()}
+    _, inter = orc.loss_cov_mixed(i64["K"], i64["pose"], i64["pts3d"], i64["pts2d"], i64["inv_std"], i64["valid"], bbox_3d=i64["bbox_3d"],
+                                  return_intermediates=True)
+    live = ins["valid"] > 0
+    sides = {"clamp": torch.linalg.vector_norm(inter["err"].detach(), dim=-1) + 1e-6 > 32,
+             "huber": (inter["e"].detach().abs() > 3 * inter["mean_abs"][:, None, :]).any(-1),
+             "weight": (i64["inv_std"] > inter["d_s"]).any(-1)}
+    loss, gu, gs, gx, _ = _run(ins, {}, True, True)
+    ref64, ref32 = oracle_run(ins, torch.float64), oracle_run(ins, torch.float32)
+    assert rel_err(gu, ref64[1]) <= 3e-4 and rel_err(gs, ref64[2]) <= 3e-4 and rel_err(gx, ref64[3]) <= 3e-4
+    assert census(ref64[1]) >= 0.25
+    _rowwise(f"{B}x{N} outliers", (loss, gu, gs, gx), ref64, ref32, samples=True)
+    for name, far in sides.items():
+        for side, mask in (("beyond", far & live), ("within", ~far & live)):
+            n = int(mask.sum())
+            print(f"{B}x{N} {name} {side}: {n} points in {int(mask.any(1).sum())} of {B} samples")
+            assert n >= 16 and bool(mask.any(1).all()), (name, side, n)  # both sides, in every sample
+            _rowwise(f"{B}x{N} {name} {side}", (loss, gu, gs, gx), ref64, ref32, where=mask)
 
 
 def test_loss_halves_equal_the_whole_batch():
@@ -237,7 +345,7 @@ def test_tiled_form_under_concurrency_and_replay():
     assert all(torch.equal(a, c) for a, c in zip(want[:4], got[:4]))
 
 
-@pytest.mark.parametrize("B,N,seed", [(2, 257, 20), (3, 1024, 21), (2, 1849, 22)])
+@pytest.mark.parametrize("B,N,seed", COV2D_SHAPES)
 def test_cov2d_dense_forms_vs_oracle_and_each_other(B, N, seed):
     """cov_2d (the covariance of the projected points) beyond N = 256: tiled=False forces the workgroup-per-sample loop
     lc_cov_loss_kernel<false, true>; tiled=True takes lc_cov_loss_tiled_kernel<true> where the workspace query is positive (N = 1024 and
@@ -266,3 +374,13 @@ def test_cov2d_dense_forms_vs_oracle_and_each_other(B, N, seed):
     loss, gu, gs, gx = (t.cpu() for t in one[:4])
     assert ((loss.double() - rl).abs() / rl.abs().clamp_min(1)).max().item() <= 3e-5
     assert rel_err(gu, ru) <= 3e-4 and rel_err(gs, rs) <= 3e-4 and rel_err(gx, rx) <= 3e-4
+    # row-wise (module comment), with this cotangent and with one spread over six decades.  cov_2d flattens the gradient sizes within a sample:
+    # under the narrow cotangent only 11 % / 35 % / 27 % of the d_pts2d points of these three batches are below 1 % of the batch's largest
+    # entry, so the census is asserted on the wide run, where the smaller samples are (55 % and more).
+    ins = dict(b, valid=valid, grad_out=go)
+    _rowwise(f"cov_2d {B}x{N}", (loss, gu, gs, gx), (rl, ru, rs, rx), oracle_run(ins, torch.float32, cov_2d=True))
+    wide = dict(ins, grad_out=wide_grad_out(B, seed))
+    got = cm.loss_cov_mixed_fused(*args, grad_out=wide["grad_out"].to(dev), cov_2d=True, tiled=True)[:4]
+    ref64 = oracle_run(wide, torch.float64, cov_2d=True)
+    assert census(ref64[1]) >= 0.25
+    _rowwise(f"cov_2d {B}x{N} wide grad_out", got, ref64, oracle_run(wide, torch.float32, cov_2d=True), samples=True)
