@@ -3,6 +3,7 @@
     lc_amd/_C/liblc_amd.so        from lc_amd/csrc/*.hip        (the hot-path C ABI, include/lc_amd.h)
     lc_amd/_C/liblc_amd_optim.so  from lc_amd/csrc/optim/*.hip  (the fused optimizer step, include/lc_amd_optim.h)
     lc_amd/_C/liblc_amd_posecov.so  from lc_amd/csrc/posecov/*.hip  (the test-time pose covariance, include/lc_amd_posecov.h)
+    lc_amd/_C/liblc_amd_render.so  from lc_amd/csrc/render/*.hip  (the depth rasteriser, include/lc_amd_render.h)
 
 Every function takes the library it works on as a `Target` (default: the hot-path library)."""
 from __future__ import annotations
@@ -40,6 +41,8 @@ MAIN = Target(CSRC, "lc_amd.h", SO_PATH, b"LC_AMD_SRC_HASH:")  # the library car
 OPTIM = Target(os.path.join(CSRC, "optim"), "lc_amd_optim.h", os.path.join(OUT_DIR, "liblc_amd_optim.so"), b"LC_AMD_OPTIM_SRC_HASH:")
 POSECOV = Target(os.path.join(CSRC, "posecov"), "lc_amd_posecov.h", os.path.join(OUT_DIR, "liblc_amd_posecov.so"), b"LC_AMD_POSECOV_SRC_HASH:")
 TARGETS = (MAIN, OPTIM, POSECOV)
+RENDER = Target(os.path.join(CSRC, "render"), "lc_amd_render.h", os.path.join(OUT_DIR, "liblc_amd_render.so"), b"LC_AMD_RENDER_SRC_HASH:")
+EXTRA_TARGETS = (RENDER,)  # built like TARGETS; a tuple of its own so that TARGETS stays the three libraries it has always named
 HASH_MARKER = MAIN.hash_marker
 
 
@@ -194,5 +197,5 @@ def build_variant(name: str, flags, verbose: bool = False) -> str:
 
 
 if __name__ == "__main__":
-    for t in TARGETS:
+    for t in TARGETS + EXTRA_TARGETS:
         print(build(force=True, verbose=True, target=t))

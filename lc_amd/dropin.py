@@ -21,6 +21,11 @@ Opt-in (`install(native_labels=True)`, or `python -m lc_amd.dropin --native-labe
 Opt-in (`install(native_optim=True)`, or `--native-optim`, in either order with `--native-labels`): the fused optimizer step --
     lib.optim.ranger.Ranger (and the name `utils.Ranger`, utils.py:10, when the reference's utils is already imported) -> lc_amd.optim.Ranger
 Without it the reference's own Ranger runs.
+
+Opt-in (`install(native_depth=MODELS_DIR)`, or `--native-depth MODELS_DIR`; implies `--native-labels`): the depth maps of the labels --
+    the models `obj_*.ply` of MODELS_DIR are uploaded once (lc_amd.gen_z.load_models) and `lc_amd.labels.set_depth_source` makes
+    annots_on_the_fly render `homo_z_out` for every batch that comes without it; dataset.BOP_Dataset._get_homo_with_depth no longer opens
+    `z_path` and _get_single_item leaves `homo_z_out` out of its blob, so a training run needs no `z_crop` directory.
 """
 from __future__ import annotations
 
@@ -31,11 +36,12 @@ import sys
 import types
 
 
-def install(patch_ptnet: bool = True, gpu_initialiser=None, native_labels: bool = False, native_optim: bool = False) -> dict:
+def install(patch_ptnet: bool = True, gpu_initialiser=None, native_labels: bool = False, native_optim: bool = False, native_depth=None) -> dict:
     """gpu_initialiser: True = also register the RANSAC-P3P kernel as `lib.pnp.cv2_solver` (same `solve` surface,
     `test.py:59,120`); None (default) = only when OpenCV cannot be imported, so that `test.py` runs without it.
     native_labels: also rebind the reference's label-preparation names to lc_amd.labels (done["labels"]).
-    native_optim: also rebind the reference's Ranger to lc_amd.optim.Ranger (done["optim"])."""
+    native_optim: also rebind the reference's Ranger to lc_amd.optim.Ranger (done["optim"]).
+    native_depth: a directory of BOP models (obj_*.ply, in mm): also native_labels, with the labels' depth rendered from them (done["depth"])."""
     from . import cov_mixed as cm
     from . import ptnet as head
     from .pnp import cer_solver, gpu_solver, pnp_ceres
@@ -107,8 +113,10 @@ def install(patch_ptnet: bool = True, gpu_initialiser=None, native_labels: bool 
             done["ptnet"] = True
         except Exception:
             done["ptnet"] = False
-    if native_labels:
+    if native_labels or native_depth:
         done["labels"] = _install_labels()
+    if native_depth:
+        done["depth"] = _install_depth(native_depth)
     if native_optim:
         done["optim"] = _install_optim()
     return done
@@ -130,6 +138,50 @@ def _install_labels() -> bool:
     return True
 
 
+def _install_depth(models_dir) -> bool:
+    """The models of `models_dir` on the current device as the labels' depth source (mm, like the poses of a BOP dataset; near and far
+    as tools/gen_z.py:75-76), and the reference's loader taken off the stored depth: `BOP_Dataset._get_homo_with_depth` (dataset.py:287-311)
+    returns an all-zero `homo_z` and mask without opening `z_path`, and `_get_single_item` delivers its blob without `homo_z_out`
+    (dataset.py:444,460) -- the missing key is what makes `annots_on_the_fly` render.  True only when the loader was rebound too."""
+    import torch
+
+    from . import gen_z, labels
+
+    meshes = gen_z.load_models(models_dir, torch.device("cuda", torch.cuda.current_device()), scale=1.0)
+    labels.set_depth_source(meshes, gen_z.NEAR * 1000.0, gen_z.FAR * 1000.0)
+    return _detach_loader_from_z_crop()
+
+
+def _detach_loader_from_z_crop() -> bool:
+    """Rebinds the two loader methods that read and deliver the stored depth (idempotent); False when the reference's `dataset` module
+    cannot be imported (then the caller's own loader has to leave `homo_z_out` out)."""
+    import numpy as np
+
+    try:
+        ref = importlib.import_module("dataset")
+        cls = ref.BOP_Dataset
+        orig_item = cls._get_single_item
+    except Exception:  # the reference's loader needs cv2, imgaug, ...; absent pieces are the caller's problem
+        return False
+    if getattr(cls, "_lc_amd_native_depth", False):
+        return True
+
+    def _get_homo_with_depth(self, annot, size_hw, fill_hole=True):
+        size_hw = tuple(size_hw)
+        return np.zeros(size_hw + (3,), dtype=np.float32), np.zeros(size_hw, dtype=np.float32)
+
+    def _get_single_item(self, index):
+        blob = orig_item(self, index)
+        if isinstance(blob, dict):
+            blob.pop("homo_z_out", None)
+        return blob
+
+    cls._get_homo_with_depth = _get_homo_with_depth
+    cls._get_single_item = _get_single_item
+    cls._lc_amd_native_depth = True
+    return True
+
+
 def _install_optim() -> bool:
     from . import optim
 
@@ -146,20 +198,28 @@ def _install_optim() -> bool:
 
 
 _FLAGS = ("--native-labels", "--native-optim")
+_VALUE_FLAGS = ("--native-depth",)
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    flags = set()
-    while argv and argv[0] in _FLAGS:
-        flags.add(argv.pop(0))
+    flags, values = set(), {}
+    while argv and (argv[0] in _FLAGS or argv[0] in _VALUE_FLAGS):
+        if argv[0] in _VALUE_FLAGS:
+            if len(argv) < 2:
+                raise SystemExit(f"lc_amd.dropin: {argv[0]} needs a value")
+            name = argv.pop(0)
+            values[name] = argv.pop(0)
+        else:
+            flags.add(argv.pop(0))
     native_labels, native_optim = "--native-labels" in flags, "--native-optim" in flags
     if not argv:
         raise SystemExit(__doc__)
     script = argv[0]
     sys.path.insert(0, os.path.dirname(os.path.abspath(script)))
     # native_optim is passed only when asked for: without the flag install() gets exactly the arguments it got before the flag existed
-    kw = dict(native_labels=native_labels, **({"native_optim": True} if native_optim else {}))
+    kw = dict(native_labels=native_labels, **({"native_optim": True} if native_optim else {}),
+              **({"native_depth": values["--native-depth"]} if "--native-depth" in values else {}))
     print("lc_amd.dropin:", install(**kw), file=sys.stderr)
     sys.argv = argv
     runpy.run_path(script, run_name="__main__")

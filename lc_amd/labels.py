@@ -10,6 +10,10 @@ A step takes two launches of lc_labels.hip -- the candidate selection of every c
 choose), then one streaming pass that writes xyz_gt and the targets -- plus the code decode at the check pixels for a binary-code head
 and the small torch ops of the quaternion.  Nothing reads a value back to the host (no .item(), no data-dependent shapes): the call can
 be captured in a graph.  HIP tensors only; `lc_amd.dropin.install(native_labels=True)` puts these names in place of the reference's.
+
+Opt-in depth source (`set_depth_source(meshes, near, far)`, `clear_depth_source()`; `lc_amd.dropin --native-depth MODELS_DIR`): a
+gt_dict WITHOUT the key `homo_z_out` gets it rendered on the device (lc_amd.render.render_homo_z_out from R_no_aug, t_no_aug, K_no_aug,
+out_K and obj_id; `msk_noc` too where it is absent).  With the key present nothing changes.
 """
 from __future__ import annotations
 
@@ -21,6 +25,50 @@ from torch import Tensor
 
 from . import _lib, floatbits
 from . import transforms as xforms
+
+
+_DEPTH_SOURCE = None  # (MeshSet, near, far, size_hw or None)
+
+
+def set_depth_source(meshes, near, far, size_hw=None):
+    """From now on `annots_on_the_fly` renders `homo_z_out` for a gt_dict that has none: `meshes` is a lc_amd.render.MeshSet whose
+    obj_ids are the dataset's, `near` / `far` are in the unit of t_no_aug and of the meshes.  The map size is `size_hw` if given, else
+    that of `msk_noc`, else that of the network's output maps."""
+    global _DEPTH_SOURCE
+    from . import render
+
+    if not isinstance(meshes, render.MeshSet):
+        raise TypeError(f"lc_amd.labels: set_depth_source takes a lc_amd.render.MeshSet, got {type(meshes)}")
+    if not float(near) < float(far):
+        raise ValueError("lc_amd.labels: set_depth_source needs near < far")
+    _DEPTH_SOURCE = (meshes, float(near), float(far), None if size_hw is None else (int(size_hw[0]), int(size_hw[1])))
+
+
+def clear_depth_source():
+    global _DEPTH_SOURCE
+    _DEPTH_SOURCE = None
+
+
+def _render_missing_depth(gt_dict, out_dict):
+    """gt_dict['homo_z_out'] (and 'msk_noc' if absent) from the depth source: dataset.py:293-311 + :444 on the fly."""
+    from . import render
+
+    meshes, near, far, size_hw = _DEPTH_SOURCE
+    if size_hw is None:
+        if 'msk_noc' in gt_dict:
+            size_hw = tuple(gt_dict['msk_noc'].shape[-2:])
+        else:
+            maps = [v for v in out_dict.values() if isinstance(v, Tensor) and v.dim() == 4]
+            if not maps:
+                raise RuntimeError("lc_amd.labels: the depth source needs a map size (set_depth_source(..., size_hw=), msk_noc or an output map)")
+            size_hw = tuple(maps[0].shape[-2:])
+    dev = meshes.device
+    hz, msk = render.render_homo_z_out(meshes, meshes.index_of(gt_dict['obj_id']), _f32("R_no_aug", gt_dict['R_no_aug'].to(dev)),
+                                       _f32("t_no_aug", gt_dict['t_no_aug'].to(dev)), _f32("K_no_aug", gt_dict['K_no_aug'].to(dev)),
+                                       _f32("out_K", gt_dict['out_K'].to(dev)), size_hw, near=near, far=far)
+    gt_dict['homo_z_out'] = hz
+    if 'msk_noc' not in gt_dict:
+        gt_dict['msk_noc'] = msk
 
 
 def _f32(name, t):
@@ -199,6 +247,8 @@ def selete_best_pose(gt_dict, out_dict, sym_aware_started):
 @torch.no_grad()
 def annots_on_the_fly(gt_dict, out_dict, cfg_global, step):
     """`losses.py:121-139`: the symmetry-aware pose and the network targets of this step, written into gt_dict."""
+    if _DEPTH_SOURCE is not None and 'homo_z_out' not in gt_dict:
+        _render_missing_depth(gt_dict, out_dict)
     sym_aware_started = step >= cfg_global.get('sym_aware_start', 0)
     Rt_best, Rt_xyz = _best(gt_dict, out_dict, sym_aware_started)
     T, bit_cnt = gt_dict.get('model_transform', None), gt_dict.get('bit_cnt', None)
