@@ -19,10 +19,12 @@ Call surface (mirrors the reference):
     lc_amd.inference.solve_pnp_with_cov  solve_pnp + the covariance and predicted error of every weighted pose
     lc_amd.render.render_depth / render_homo_z_out   <- tools/gen_z.py:153 (the EGL renderer) + dataset.py:287-311,444 (depth rasteriser, liblc_amd_render.so)
     lc_amd.gen_z                         <- tools/gen_z.py (python -m lc_amd.gen_z: the z_crop files without OpenGL)
+    lc_amd.crops.warp_affine / test_item / finish_blob   <- dataset.py:409-411 cv2.warpAffine + .div(255) + test.py:163 Normalize (zoom-in crops, liblc_amd_crop.so)
     lc_amd.dropin                        run the reference's train.py / test.py on all of the above without editing them
 Native code: lc_amd/csrc/*.hip -> lc_amd/_C/liblc_amd.so (C ABI in include/lc_amd.h);
 lc_amd/csrc/optim/*.hip -> lc_amd/_C/liblc_amd_optim.so (include/lc_amd_optim.h);
 lc_amd/csrc/posecov/*.hip -> lc_amd/_C/liblc_amd_posecov.so (include/lc_amd_posecov.h);
-lc_amd/csrc/render/*.hip -> lc_amd/_C/liblc_amd_render.so (include/lc_amd_render.h).
+lc_amd/csrc/render/*.hip -> lc_amd/_C/liblc_amd_render.so (include/lc_amd_render.h);
+lc_amd/csrc/crop/*.hip -> lc_amd/_C/liblc_amd_crop.so (include/lc_amd_crop.h).
 """
 __version__ = "0.1.0"

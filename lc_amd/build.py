@@ -4,6 +4,7 @@
     lc_amd/_C/liblc_amd_optim.so  from lc_amd/csrc/optim/*.hip  (the fused optimizer step, include/lc_amd_optim.h)
     lc_amd/_C/liblc_amd_posecov.so  from lc_amd/csrc/posecov/*.hip  (the test-time pose covariance, include/lc_amd_posecov.h)
     lc_amd/_C/liblc_amd_render.so  from lc_amd/csrc/render/*.hip  (the depth rasteriser, include/lc_amd_render.h)
+    lc_amd/_C/liblc_amd_crop.so  from lc_amd/csrc/crop/*.hip  (the zoom-in crops, include/lc_amd_crop.h)
 
 Every function takes the library it works on as a `Target` (default: the hot-path library)."""
 from __future__ import annotations
@@ -43,7 +44,13 @@ POSECOV = Target(os.path.join(CSRC, "posecov"), "lc_amd_posecov.h", os.path.join
 TARGETS = (MAIN, OPTIM, POSECOV)
 RENDER = Target(os.path.join(CSRC, "render"), "lc_amd_render.h", os.path.join(OUT_DIR, "liblc_amd_render.so"), b"LC_AMD_RENDER_SRC_HASH:")
 EXTRA_TARGETS = (RENDER,)  # built like TARGETS; a tuple of its own so that TARGETS stays the three libraries it has always named
+CROP = Target(os.path.join(CSRC, "crop"), "lc_amd_crop.h", os.path.join(OUT_DIR, "liblc_amd_crop.so"), b"LC_AMD_CROP_SRC_HASH:")
 HASH_MARKER = MAIN.hash_marker
+
+
+def all_targets():
+    """Every library of the package: TARGETS and EXTRA_TARGETS as they have always been, and the libraries added since."""
+    return TARGETS + EXTRA_TARGETS + (CROP,)
 
 
 def sources(target: Target = MAIN):
@@ -197,5 +204,5 @@ def build_variant(name: str, flags, verbose: bool = False) -> str:
 
 
 if __name__ == "__main__":
-    for t in TARGETS + EXTRA_TARGETS:
+    for t in all_targets():
         print(build(force=True, verbose=True, target=t))

@@ -1,0 +1,274 @@
+// Zoom-in crops: exact integer affine warps of uint8 frames, one launch (liblc_amd_crop.so, C ABI and the exact definition of the
+// result in include/lc_amd_crop.h).
+//
+// What the reference's loader does per instance on the host with cv2.warpAffine (dataset.py:409-411, 425-426) followed by
+// `.to(float32).div(255)` and transforms.Normalize (test.py:163): here every crop of a batch is cut from frames that were uploaded
+// once, in OpenCV's published fixed-point scheme for 8-bit images (coordinates on a 1/1024 px grid, bilinear weights on a 1/32 px
+// grid), which is pure integer arithmetic after the inverse matrix.
+//
+//   one workgroup of four waves per (row, band of crop rows).  Thread 0 forms the row's inverse matrix in fp64 and judges the row;
+//   all threads fill a 256 C-entry table of the FINISHED output values in LDS (there are only 256 values per channel, so the
+//   division by 255 and the normalisation leave the pixel loop).  A thread then owns four consecutive x (its two x terms are formed
+//   once) and walks the band's rows: four taps per pixel read as bytes, a blend in 32-bit integers, a table look-up per channel,
+//   and one store of four pixels per channel plane (16 bytes for fp32, 8 for the 16-bit types, 4 for uint8; element by element
+//   where w is no multiple of four or the output is not aligned).
+//
+// The coordinate arithmetic is written with __dmul_rn / __dadd_rn: the library is built with -ffp-contract=on, and m01 * y + b1 in one
+// expression would be fused and can move X by one.
+//
+// Bounds: every tap is range-checked against the frame on its own (that IS the border rule), a bad row sees a frame of size zero, and
+// the frame index is checked before it is used, so that no input value can make the launch read or write outside its arrays.
+//
+// Self-contained on purpose: the library's source hash covers this directory and its header only.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+#include "../../../include/lc_amd_crop.h"
+
+#ifndef LC_AMD_CROP_SRC_HASH
+#define LC_AMD_CROP_SRC_HASH "unrecorded"
+#endif
+
+namespace {
+
+const char kSrcHash[] = "LC_AMD_CROP_SRC_HASH:" LC_AMD_CROP_SRC_HASH;
+thread_local std::string g_err;
+
+int fail(int code, std::string msg) {
+    g_err = std::move(msg);
+    return code;
+}
+
+constexpr int kThreads = 256;
+constexpr int kMinBand = 16;           // crop rows per workgroup (more where a pass of the workgroup covers more)
+constexpr double kAbScale = 1024.0;    // 1 << AB_BITS
+constexpr double kFixLimit = 1073741824.0;  // 2^30
+
+struct Params {
+    const unsigned char* frames;
+    const int* frame_index;
+    const float* M;
+    void* out;
+    int* info;
+    int F, H, W, B, h, w;
+    int band, nbands;  // crop rows per workgroup, workgroups per row of the batch
+    int lg_tx;         // log2 of the threads along x
+    int vec;           // four-pixel stores are possible (w % 4 == 0 and the output is aligned to them)
+    int normalize;
+    float mean[3], std[3];
+};
+
+template <int DT> struct Store { using type = unsigned short; };
+template <> struct Store<LC_CROP_U8> { using type = unsigned char; };
+template <> struct Store<LC_CROP_F32> { using type = float; };
+
+template <typename T> struct alignas(4 * sizeof(T)) Vec4 { T v[4]; };
+
+// The finished output value of byte v in channel c: v / 255, then (. - mean) / std, each an IEEE fp32 operation; a 16-bit type is
+// rounded once (nearest even) from that fp32.
+template <int DT>
+__device__ inline typename Store<DT>::type finish(int v, int c, const Params& p) {
+    if constexpr (DT == LC_CROP_U8) {
+        return (unsigned char)v;
+    } else {
+        float q = __fdiv_rn((float)v, 255.0f);
+        if (p.normalize) {
+            q = __fsub_rn(q, p.mean[c]);
+            q = __fdiv_rn(q, p.std[c]);
+        }
+        if constexpr (DT == LC_CROP_F32) {
+            return q;
+        } else if constexpr (DT == LC_CROP_F16) {
+            return __builtin_bit_cast(unsigned short, (_Float16)q);
+        } else {
+            const unsigned u = __float_as_uint(q);
+            if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)0x7fc0;
+            return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+        }
+    }
+}
+
+// rint (half to even), clamped to +-2^30, as an integer.  fmax / fmin also turn a NaN into a bound.
+__device__ inline int fix(double v) {
+    return (int)fmin(fmax(rint(v), -kFixLimit), kFixLimit);
+}
+
+template <int DT, int C, bool LINEAR>
+__global__ __launch_bounds__(kThreads) void lc_crop_warp_kernel(const Params p) {
+    using T = typename Store<DT>::type;
+    constexpr bool kTable = DT != LC_CROP_U8;
+    __shared__ T table[kTable ? 256 * C : 1];
+    __shared__ double s_inv[6];
+    __shared__ int s_frame;  // -1 = bad row
+
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / p.nbands, band = blockIdx.x - b * p.nbands;
+    if (tid == 0) {
+        const int f = p.frame_index ? p.frame_index[b] : b;
+        bool ok = f >= 0 && f < p.F;
+        double M[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            const float m = p.M[6 * (size_t)b + k];
+            ok = ok && (__float_as_uint(m) & 0x7f800000u) != 0x7f800000u;
+            M[k] = (double)m;
+        }
+        double D = __dadd_rn(__dmul_rn(M[0], M[4]), -__dmul_rn(M[1], M[3]));
+        D = D != 0.0 ? 1.0 / D : 0.0;
+        const double m00 = __dmul_rn(M[4], D), m01 = __dmul_rn(-M[1], D), m10 = __dmul_rn(-M[3], D), m11 = __dmul_rn(M[0], D);
+        s_inv[0] = m00;
+        s_inv[1] = m01;
+        s_inv[2] = __dadd_rn(__dmul_rn(-m00, M[2]), -__dmul_rn(m01, M[5]));
+        s_inv[3] = m10;
+        s_inv[4] = m11;
+        s_inv[5] = __dadd_rn(__dmul_rn(-m10, M[2]), -__dmul_rn(m11, M[5]));
+        s_frame = ok ? f : -1;
+        if (band == 0 && p.info) p.info[b] = ok ? 0 : -1;
+    }
+    if constexpr (kTable) {
+        for (int i = tid; i < 256 * C; i += kThreads) table[i] = finish<DT>(i & 255, i >> 8, p);
+    }
+    __syncthreads();
+
+    const int frame = s_frame;
+    const int H = frame >= 0 ? p.H : 0, W = frame >= 0 ? p.W : 0;  // a bad row: every tap is outside
+    const unsigned char* src = p.frames + (size_t)(frame >= 0 ? frame : 0) * p.H * p.W * C;
+    const double m00 = s_inv[0], m01 = s_inv[1], b1 = s_inv[2], m10 = s_inv[3], m11 = s_inv[4], b2 = s_inv[5];
+    T* out = static_cast<T*>(p.out) + (size_t)b * C * p.h * p.w;
+    const size_t plane = (size_t)p.h * p.w;
+
+    const int TX = 1 << p.lg_tx, TY = kThreads >> p.lg_tx;
+    const int tx = tid & (TX - 1), ty = tid >> p.lg_tx;
+    const int quads = (p.w + 3) >> 2;
+    const int y_end = min(p.h, (band + 1) * p.band);
+    constexpr long long kDelta = LINEAR ? 16 : 512;
+
+    auto tap = [&](int xx, int yy, int (&s)[C]) {
+        const bool in = (unsigned)xx < (unsigned)W && (unsigned)yy < (unsigned)H;
+        const unsigned char* q = src + ((size_t)(in ? yy : 0) * W + (in ? xx : 0)) * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) s[c] = in ? (int)q[c] : 0;
+    };
+
+    for (int xq = tx; xq < quads; xq += TX) {
+        const int x0 = xq << 2;
+        int ax[4], ay[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double x = (double)(x0 + j);
+            ax[j] = fix(__dmul_rn(__dmul_rn(m00, x), kAbScale));
+            ay[j] = fix(__dmul_rn(__dmul_rn(m10, x), kAbScale));
+        }
+        for (int y = band * p.band + ty; y < y_end; y += TY) {
+            const double yd = (double)y;
+            const long long X0 = (long long)fix(__dmul_rn(__dadd_rn(__dmul_rn(m01, yd), b1), kAbScale)) + kDelta;
+            const long long Y0 = (long long)fix(__dmul_rn(__dadd_rn(__dmul_rn(m11, yd), b2), kAbScale)) + kDelta;
+            Vec4<T> res[C];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long long X = X0 + ax[j], Y = Y0 + ay[j];
+                int v[C];
+                if constexpr (LINEAR) {
+                    const int Xs = (int)(X >> 5), Ys = (int)(Y >> 5);
+                    const int sx = Xs >> 5, sy = Ys >> 5, fx = Xs & 31, fy = Ys & 31;
+                    int s00[C], s01[C], s10[C], s11[C];
+                    tap(sx, sy, s00);
+                    tap(sx + 1, sy, s01);
+                    tap(sx, sy + 1, s10);
+                    tap(sx + 1, sy + 1, s11);
+                    const int w00 = (32 - fx) * (32 - fy), w01 = fx * (32 - fy), w10 = (32 - fx) * fy, w11 = fx * fy;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) v[c] = (w00 * s00[c] + w01 * s01[c] + w10 * s10[c] + w11 * s11[c] + 512) >> 10;
+                } else {
+                    tap((int)(X >> 10), (int)(Y >> 10), v);
+                }
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    if constexpr (kTable) res[c].v[j] = table[c * 256 + v[c]];
+                    else res[c].v[j] = (T)v[c];
+                }
+            }
+            const size_t o = (size_t)y * p.w + x0;
+            if (p.vec) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) *reinterpret_cast<Vec4<T>*>(out + c * plane + o) = res[c];
+            } else {
+#pragma unroll
+                for (int c = 0; c < C; ++c)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (x0 + j < p.w) out[c * plane + o + j] = res[c].v[j];
+            }
+        }
+    }
+}
+
+template <int DT, int C>
+void launch_interp(const Params& p, int interp, unsigned blocks, hipStream_t s) {
+    if (interp == LC_CROP_LINEAR) hipLaunchKernelGGL((lc_crop_warp_kernel<DT, C, true>), dim3(blocks), dim3(kThreads), 0, s, p);
+    else hipLaunchKernelGGL((lc_crop_warp_kernel<DT, C, false>), dim3(blocks), dim3(kThreads), 0, s, p);
+}
+
+template <int DT>
+void launch_channels(const Params& p, int C, int interp, unsigned blocks, hipStream_t s) {
+    if (C == 3) launch_interp<DT, 3>(p, interp, blocks, s);
+    else launch_interp<DT, 1>(p, interp, blocks, s);
+}
+
+}  // namespace
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int lc_amd_crop_version(void) { return LC_AMD_CROP_VERSION; }
+const char* lc_amd_crop_source_hash(void) { return kSrcHash + sizeof("LC_AMD_CROP_SRC_HASH:") - 1; }
+const char* lc_amd_crop_last_error(void) { return g_err.c_str(); }
+
+int lc_crop_warp_u8(const unsigned char* frames, int F, int H, int W, int C, const int* frame_index, const float* M, int B, int h, int w,
+                    int interp, int out_dtype, const float* mean, const float* std, void* out, int* info, void* stream) {
+    if (B < 0) return fail(1, "lc_crop_warp_u8: B < 0");
+    if (B == 0) return 0;
+    if (C != 1 && C != 3) return fail(2, "lc_crop_warp_u8: C must be 1 or 3, got " + std::to_string(C));
+    if (F < 0) return fail(3, "lc_crop_warp_u8: F < 0");
+    if (H < 1 || W < 1 || H > LC_CROP_MAX_SIZE || W > LC_CROP_MAX_SIZE || h < 1 || w < 1 || h > LC_CROP_MAX_SIZE || w > LC_CROP_MAX_SIZE)
+        return fail(4, "lc_crop_warp_u8: frame and crop sizes must be in [1, " + std::to_string(LC_CROP_MAX_SIZE) + "], got " + std::to_string(H) +
+                           " x " + std::to_string(W) + " -> " + std::to_string(h) + " x " + std::to_string(w));
+    if (interp != LC_CROP_NEAREST && interp != LC_CROP_LINEAR) return fail(5, "lc_crop_warp_u8: interp must be LC_CROP_NEAREST or LC_CROP_LINEAR");
+    if (out_dtype < LC_CROP_U8 || out_dtype > LC_CROP_BF16) return fail(6, "lc_crop_warp_u8: unknown out_dtype " + std::to_string(out_dtype));
+    if ((mean == nullptr) != (std == nullptr)) return fail(7, "lc_crop_warp_u8: mean and std come together");
+    if (mean && out_dtype == LC_CROP_U8) return fail(7, "lc_crop_warp_u8: mean and std need a float output");
+    if (!M || !out || (F > 0 && !frames)) return fail(8, "lc_crop_warp_u8: frames, M and out must not be NULL");
+    Params p{};
+    p.frames = frames;
+    p.frame_index = frame_index;
+    p.M = M;
+    p.out = out;
+    p.info = info;
+    p.F = F, p.H = H, p.W = W, p.B = B, p.h = h, p.w = w;
+    const int quads = (w + 3) / 4;
+    while ((1 << p.lg_tx) < quads && (1 << p.lg_tx) < kThreads) ++p.lg_tx;
+    const int rows_per_pass = kThreads >> p.lg_tx;
+    p.band = rows_per_pass > kMinBand ? rows_per_pass : kMinBand;
+    p.nbands = (h + p.band - 1) / p.band;
+    const size_t elem = out_dtype == LC_CROP_U8 ? 1 : out_dtype == LC_CROP_F32 ? 4 : 2;
+    p.vec = (w % 4 == 0) && (reinterpret_cast<uintptr_t>(out) % (4 * elem) == 0);
+    p.normalize = mean != nullptr;
+    for (int c = 0; c < C && mean; ++c) p.mean[c] = mean[c], p.std[c] = std[c];
+    const long long blocks = (long long)B * p.nbands;
+    if (blocks > 0x7fffffffLL) return fail(9, "lc_crop_warp_u8: too many rows and bands for one launch");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (out_dtype) {
+        case LC_CROP_U8: launch_channels<LC_CROP_U8>(p, C, interp, (unsigned)blocks, s); break;
+        case LC_CROP_F32: launch_channels<LC_CROP_F32>(p, C, interp, (unsigned)blocks, s); break;
+        case LC_CROP_F16: launch_channels<LC_CROP_F16>(p, C, interp, (unsigned)blocks, s); break;
+        default: launch_channels<LC_CROP_BF16>(p, C, interp, (unsigned)blocks, s); break;
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(10, std::string("lc_crop_warp_u8: launch: ") + hipGetErrorString(e));
+    return 0;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

@@ -26,6 +26,13 @@ Opt-in (`install(native_depth=MODELS_DIR)`, or `--native-depth MODELS_DIR`; impl
     the models `obj_*.ply` of MODELS_DIR are uploaded once (lc_amd.gen_z.load_models) and `lc_amd.labels.set_depth_source` makes
     annots_on_the_fly render `homo_z_out` for every batch that comes without it; dataset.BOP_Dataset._get_homo_with_depth no longer opens
     `z_path` and _get_single_item leaves `homo_z_out` out of its blob, so a training run needs no `z_crop` directory.
+
+Opt-in (`install(native_crops=True)`, or `--native-crops`): the zoom-in crop of the test-time loader (the reference's `dataset` module must still import,
+    which needs a cv2 module, imgaug and pycocotools: lc_amd.crops.test_item makes no OpenCV call, `import dataset` does) --
+    dataset.BOP_Dataset._get_single_item of a dataset with `training == False` -> lc_amd.crops.test_item (the frame as uint8 and the
+    crop's matrix instead of `rgb_in`); utils.xfer_to (and the name `test.xfer_to`, test.py:9, when that module is already imported)
+    -> the same transfer followed by lc_amd.crops.finish_blob, which cuts `rgb_in` on the device.  Training datasets keep the
+    reference's method.  The frames of one batch must share a size (default_collate stacks them).
 """
 from __future__ import annotations
 
@@ -36,12 +43,14 @@ import sys
 import types
 
 
-def install(patch_ptnet: bool = True, gpu_initialiser=None, native_labels: bool = False, native_optim: bool = False, native_depth=None) -> dict:
+def install(patch_ptnet: bool = True, gpu_initialiser=None, native_labels: bool = False, native_optim: bool = False, native_depth=None,
+            native_crops: bool = False) -> dict:
     """gpu_initialiser: True = also register the RANSAC-P3P kernel as `lib.pnp.cv2_solver` (same `solve` surface,
     `test.py:59,120`); None (default) = only when OpenCV cannot be imported, so that `test.py` runs without it.
     native_labels: also rebind the reference's label-preparation names to lc_amd.labels (done["labels"]).
     native_optim: also rebind the reference's Ranger to lc_amd.optim.Ranger (done["optim"]).
-    native_depth: a directory of BOP models (obj_*.ply, in mm): also native_labels, with the labels' depth rendered from them (done["depth"])."""
+    native_depth: a directory of BOP models (obj_*.ply, in mm): also native_labels, with the labels' depth rendered from them (done["depth"]).
+    native_crops: also take the test-time loader's zoom-in crop onto the device (done["crops"])."""
     from . import cov_mixed as cm
     from . import ptnet as head
     from .pnp import cer_solver, gpu_solver, pnp_ceres
@@ -119,6 +128,8 @@ def install(patch_ptnet: bool = True, gpu_initialiser=None, native_labels: bool 
         done["depth"] = _install_depth(native_depth)
     if native_optim:
         done["optim"] = _install_optim()
+    if native_crops:
+        done["crops"] = _install_crops()
     return done
 
 
@@ -182,6 +193,51 @@ def _detach_loader_from_z_crop() -> bool:
     return True
 
 
+def _install_crops() -> bool:
+    """Rebinds the test-time loader and the transfer (idempotent); False when the reference's `dataset` or `utils` cannot be imported.
+    `finish_blob` needs the size of the network's input, which no blob carries: the rebound `collate_fn` (called where the loader is
+    built, utils.py:37) and the rebound `_get_single_item` note it from the dataset object."""
+    from . import crops
+
+    try:
+        ref = importlib.import_module("dataset")
+        utils = importlib.import_module("utils")
+        cls = ref.BOP_Dataset
+        orig_item, orig_collate, orig_xfer = cls._get_single_item, cls.collate_fn, utils.xfer_to
+    except Exception:  # the reference's loader needs imgaug, pycocotools, ...; absent pieces are the caller's problem
+        return False
+
+    def note_size(ds):
+        w, h = ds.net_input_wh
+        crops.set_net_input_hw((h, w))
+
+    if not getattr(cls, "_lc_amd_native_crops", False):
+        def _get_single_item(self, index):
+            if self.training:
+                return orig_item(self, index)
+            note_size(self)
+            return crops.test_item(self, index)
+
+        def collate_fn(self):
+            if not self.training:
+                note_size(self)
+            return orig_collate(self)
+
+        cls._get_single_item = _get_single_item
+        cls.collate_fn = collate_fn
+        cls._lc_amd_native_crops = True
+    if not getattr(orig_xfer, "_lc_amd_native_crops", False):
+        def xfer_to(pack, device, non_blocking=True):
+            return crops.finish_blob(orig_xfer(pack, device, non_blocking=non_blocking))
+
+        xfer_to._lc_amd_native_crops = True
+        utils.xfer_to = xfer_to
+        test = sys.modules.get("test")
+        if test is not None and getattr(test, "xfer_to", None) is orig_xfer:
+            test.xfer_to = xfer_to  # `from utils import xfer_to` (test.py:9) ran before the rebinding
+    return True
+
+
 def _install_optim() -> bool:
     from . import optim
 
@@ -197,7 +253,7 @@ def _install_optim() -> bool:
     return True
 
 
-_FLAGS = ("--native-labels", "--native-optim")
+_FLAGS = ("--native-labels", "--native-optim", "--native-crops")
 _VALUE_FLAGS = ("--native-depth",)
 
 
@@ -217,9 +273,10 @@ def main(argv=None):
         raise SystemExit(__doc__)
     script = argv[0]
     sys.path.insert(0, os.path.dirname(os.path.abspath(script)))
-    # native_optim is passed only when asked for: without the flag install() gets exactly the arguments it got before the flag existed
+    # native_optim (and native_crops) is passed only when asked for: without the flag install() gets exactly the arguments it got before the flag existed
     kw = dict(native_labels=native_labels, **({"native_optim": True} if native_optim else {}),
-              **({"native_depth": values["--native-depth"]} if "--native-depth" in values else {}))
+              **({"native_depth": values["--native-depth"]} if "--native-depth" in values else {}),
+              **({"native_crops": True} if "--native-crops" in flags else {}))
     print("lc_amd.dropin:", install(**kw), file=sys.stderr)
     sys.argv = argv
     runpy.run_path(script, run_name="__main__")
