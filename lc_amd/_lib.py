@@ -75,13 +75,20 @@ def lib_path() -> str:
     return os.environ.get("LC_AMD_LIB", _build.SO_PATH)
 
 
-def load(build_if_missing: bool = True):
-    """Load (building first if the .so is absent and hipcc is available). Raises if it cannot be loaded."""
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    path = lib_path()
-    if path == _build.SO_PATH and _build.is_stale():
+def _open(path: str, signatures):
+    lib = ctypes.CDLL(path)
+    for name, (res, args) in signatures.items():
+        fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
+def load_target(target, signatures, build_if_missing: bool = True):
+    """The library of `target` with `signatures` set on it (building first if it is absent or stale and hipcc is available).
+    The one loader behind every module's cached `load()`.  Raises if the library cannot be loaded."""
+    path = target.so_path
+    if _build.is_stale(target):
         # missing, or built from other .hip/.h contents than the ones on disk (the library carries the hash of its sources):
         # rebuild (hipcc cross-compiles without a GPU); never silently run a library that ignores edited sources
         if os.path.exists(path) and not _build.hipcc_available():
@@ -89,8 +96,8 @@ def load(build_if_missing: bool = True):
             # from the sources next to it is refused unless the caller says so explicitly (a warning is lost wherever stderr is discarded)
             if os.environ.get("LC_AMD_ALLOW_STALE") != "1":
                 raise RuntimeError(f"lc_amd: {path} was built from other sources than the ones next to it (embedded hash "
-                                   f"{_build.embedded_hash(path)}, sources {_build.source_hash()}) and hipcc is not available to rebuild it; "
-                                   f"set LC_AMD_ALLOW_STALE=1 to load it as it is")
+                                   f"{_build.embedded_hash(path, target.hash_marker)}, sources {_build.source_hash(target)}) and hipcc is not "
+                                   f"available to rebuild it; set LC_AMD_ALLOW_STALE=1 to load it as it is")
             import warnings
 
             warnings.warn(f"lc_amd: loading {path} although it was built from other sources than the ones next to it (LC_AMD_ALLOW_STALE=1)")
@@ -98,19 +105,27 @@ def load(build_if_missing: bool = True):
             raise RuntimeError(f"lc_amd: {path} is missing or stale; run `python __graft_entry__.py build`")
         else:
             try:
-                _build.build()
+                _build.build(target=target)
             except Exception as e:  # noqa: BLE001
-                raise RuntimeError(f"lc_amd: {path} is missing or older than lc_amd/csrc and could not be rebuilt ({e}); "
+                src_dir = os.path.relpath(target.src_dir, os.path.dirname(_build.PKG)).replace(os.sep, "/")
+                raise RuntimeError(f"lc_amd: {path} is missing or older than {src_dir} and could not be rebuilt ({e}); "
                                    f"run `python __graft_entry__.py build` where hipcc is available") from e
+    return _open(path, signatures)
+
+
+def load(build_if_missing: bool = True):
+    """liblc_amd.so, loaded on first use by `load_target`; LC_AMD_LIB names another build of it (a variant), loaded as it is."""
+    global _LIB
+    if _LIB is not None:
+        return _LIB
+    path = lib_path()
+    if path == _build.SO_PATH:
+        _LIB = load_target(_build.MAIN, _SIGNATURES, build_if_missing)
     elif not os.path.exists(path):
         raise RuntimeError(f"lc_amd: LC_AMD_LIB={path} does not exist")
-    lib = ctypes.CDLL(path)
-    for name, (res, args) in _SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
-        fn.restype = res
-        fn.argtypes = args
-    _LIB = lib
-    return lib
+    else:
+        _LIB = _open(path, _SIGNATURES)
+    return _LIB
 
 
 def check(rc: int, what: str):

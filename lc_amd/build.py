@@ -1,11 +1,13 @@
-"""Builds the native libraries with hipcc for gfx950 (cross-compiles without a GPU):
+"""Builds the native libraries with hipcc for gfx950 (cross-compiles without a GPU), each from the .hip files of one directory:
 
-    lc_amd/_C/liblc_amd.so        from lc_amd/csrc/*.hip        (the hot-path C ABI, include/lc_amd.h)
-    lc_amd/_C/liblc_amd_optim.so  from lc_amd/csrc/optim/*.hip  (the fused optimizer step, include/lc_amd_optim.h)
-    lc_amd/_C/liblc_amd_posecov.so  from lc_amd/csrc/posecov/*.hip  (the test-time pose covariance, include/lc_amd_posecov.h)
-    lc_amd/_C/liblc_amd_render.so  from lc_amd/csrc/render/*.hip  (the depth rasteriser, include/lc_amd_render.h)
-    lc_amd/_C/liblc_amd_crop.so  from lc_amd/csrc/crop/*.hip  (the zoom-in crops, include/lc_amd_crop.h)
+    name     library                         sources                  C ABI
+    main     lc_amd/_C/liblc_amd.so          lc_amd/csrc/*.hip        include/lc_amd.h          the hot path
+    optim    lc_amd/_C/liblc_amd_optim.so    lc_amd/csrc/optim/       include/lc_amd_optim.h    the fused optimizer step
+    posecov  lc_amd/_C/liblc_amd_posecov.so  lc_amd/csrc/posecov/     include/lc_amd_posecov.h  the test-time pose covariance
+    render   lc_amd/_C/liblc_amd_render.so   lc_amd/csrc/render/      include/lc_amd_render.h   the depth rasteriser
+    crop     lc_amd/_C/liblc_amd_crop.so     lc_amd/csrc/crop/        include/lc_amd_crop.h     the zoom-in crops
 
+A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`).
 Every function takes the library it works on as a `Target` (default: the hot-path library)."""
 from __future__ import annotations
 
@@ -30,27 +32,39 @@ def _hipcc() -> str:
 
 
 class Target(NamedTuple):
-    """One library: the directory of its sources (non-recursive globs), its public header, where it goes, and the marker in front of
-    the source hash it carries (compiled in as the macro named by the marker without its colon)."""
+    """One library: its short name, the directory of its sources (non-recursive globs), its public header, where it goes, the marker
+    in front of the source hash it carries (compiled in as the macro named by the marker without its colon), and the headers it
+    includes from lc_amd/csrc/shared/ (hashed along with its own directory)."""
+    name: str
     src_dir: str
     header: str
     so_path: str
     hash_marker: bytes
+    shared: tuple = ()
 
 
-MAIN = Target(CSRC, "lc_amd.h", SO_PATH, b"LC_AMD_SRC_HASH:")  # the library carries the hash of its own sources (lc_capi.hip: lc_amd_source_hash)
-OPTIM = Target(os.path.join(CSRC, "optim"), "lc_amd_optim.h", os.path.join(OUT_DIR, "liblc_amd_optim.so"), b"LC_AMD_OPTIM_SRC_HASH:")
-POSECOV = Target(os.path.join(CSRC, "posecov"), "lc_amd_posecov.h", os.path.join(OUT_DIR, "liblc_amd_posecov.so"), b"LC_AMD_POSECOV_SRC_HASH:")
-TARGETS = (MAIN, OPTIM, POSECOV)
-RENDER = Target(os.path.join(CSRC, "render"), "lc_amd_render.h", os.path.join(OUT_DIR, "liblc_amd_render.so"), b"LC_AMD_RENDER_SRC_HASH:")
-EXTRA_TARGETS = (RENDER,)  # built like TARGETS; a tuple of its own so that TARGETS stays the three libraries it has always named
-CROP = Target(os.path.join(CSRC, "crop"), "lc_amd_crop.h", os.path.join(OUT_DIR, "liblc_amd_crop.so"), b"LC_AMD_CROP_SRC_HASH:")
+SHARED = os.path.join(CSRC, "shared")
+SHARED_H = os.path.join(SHARED, "lc_shared.h")  # the fp64 cross-lane layer: the order-defining reductions of MAIN and POSECOV
+
+
+def _side(name: str, shared: tuple = ()) -> Target:
+    """A side library, everything following from its name: csrc/<name>, include/lc_amd_<name>.h, _C/liblc_amd_<name>.so."""
+    return Target(name, os.path.join(CSRC, name), f"lc_amd_{name}.h", os.path.join(OUT_DIR, f"liblc_amd_{name}.so"),
+                  f"LC_AMD_{name.upper()}_SRC_HASH:".encode(), shared)
+
+
+MAIN = Target("main", CSRC, "lc_amd.h", SO_PATH, b"LC_AMD_SRC_HASH:", (SHARED_H,))  # the library carries the hash of its own sources (lc_capi.hip: lc_amd_source_hash)
+OPTIM = _side("optim")
+POSECOV = _side("posecov", (SHARED_H,))
+RENDER = _side("render")
+CROP = _side("crop")
+_ALL = (MAIN, OPTIM, POSECOV, RENDER, CROP)
 HASH_MARKER = MAIN.hash_marker
 
 
 def all_targets():
-    """Every library of the package: TARGETS and EXTRA_TARGETS as they have always been, and the libraries added since."""
-    return TARGETS + EXTRA_TARGETS + (CROP,)
+    """Every library of the package, in build order."""
+    return _ALL
 
 
 def sources(target: Target = MAIN):
@@ -58,7 +72,7 @@ def sources(target: Target = MAIN):
 
 
 def _deps(target: Target = MAIN):
-    return sources(target) + sorted(glob.glob(os.path.join(target.src_dir, "*.h"))) + [os.path.join(os.path.dirname(PKG), "include", target.header)]
+    return sources(target) + sorted(glob.glob(os.path.join(target.src_dir, "*.h"))) + [os.path.join(os.path.dirname(PKG), "include", target.header)] + list(target.shared)
 
 
 def source_hash(target: Target = MAIN) -> str:

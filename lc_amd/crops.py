@@ -19,7 +19,6 @@ from __future__ import annotations
 import ctypes
 import logging
 import math
-import os
 from ctypes import c_int, c_void_p
 from operator import itemgetter
 
@@ -47,37 +46,12 @@ _SIGNATURES = {
 
 
 def load(build_if_missing: bool = True):
-    """liblc_amd_crop.so, loaded on first use with the staleness rule of `_lib.load()`: a library built from other sources than the
-    ones next to it is rebuilt, or refused where hipcc is absent (unless LC_AMD_ALLOW_STALE=1)."""
+    """liblc_amd_crop.so, loaded on first use by `_lib.load_target`: a library built from other sources than the ones next to it is
+    rebuilt, or refused where hipcc is absent (unless LC_AMD_ALLOW_STALE=1)."""
     global _LIB
-    if _LIB is not None:
-        return _LIB
-    target = _build.CROP
-    path = target.so_path
-    if _build.is_stale(target):
-        if os.path.exists(path) and not _build.hipcc_available():
-            if os.environ.get("LC_AMD_ALLOW_STALE") != "1":
-                raise RuntimeError(f"lc_amd: {path} was built from other sources than the ones next to it (embedded hash "
-                                   f"{_build.embedded_hash(path, target.hash_marker)}, sources {_build.source_hash(target)}) and hipcc is not "
-                                   f"available to rebuild it; set LC_AMD_ALLOW_STALE=1 to load it as it is")
-            import warnings
-
-            warnings.warn(f"lc_amd: loading {path} although it was built from other sources than the ones next to it (LC_AMD_ALLOW_STALE=1)")
-        elif not build_if_missing:
-            raise RuntimeError(f"lc_amd: {path} is missing or stale; run `python __graft_entry__.py build`")
-        else:
-            try:
-                _build.build(target=target)
-            except Exception as e:  # noqa: BLE001
-                raise RuntimeError(f"lc_amd: {path} is missing or older than lc_amd/csrc/crop and could not be rebuilt ({e}); "
-                                   f"run `python __graft_entry__.py build` where hipcc is available") from e
-    lib = ctypes.CDLL(path)
-    for name, (res, args) in _SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _LIB = lib
-    return lib
+    if _LIB is None:
+        _LIB = _lib.load_target(_build.CROP, _SIGNATURES, build_if_missing)
+    return _LIB
 
 
 def _require(name, t, dtype, what):

@@ -20,7 +20,7 @@ __global__ __launch_bounds__(64) void lc_kpt_nll_kernel(const KptParams p) {
         for (int i = 0; i < 9; ++i) pc.K[i] = Kp[i];
         const double q[4] = {ps[0], ps[1], ps[2], ps[3]};
         const double irho = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-        loss::quat_matrix(q, 2.0 * irho, pc.R);
+        quat_matrix(q, 2.0 * irho, pc.R);
         pc.rho = 0;
         pc.t[0] = ps[4]; pc.t[1] = ps[5]; pc.t[2] = ps[6];
     }

@@ -60,13 +60,6 @@ struct PoseConst {
     double t[3];
 };
 
-__device__ __forceinline__ void quat_matrix(const double q[4], double two_s, double R[9]) {
-    const double r = q[0], i = q[1], j = q[2], k = q[3];
-    R[0] = 1 - two_s * (j * j + k * k); R[1] = two_s * (i * j - k * r); R[2] = two_s * (i * k + j * r);
-    R[3] = two_s * (i * j + k * r); R[4] = 1 - two_s * (i * i + k * k); R[5] = two_s * (j * k - i * r);
-    R[6] = two_s * (i * k - j * r); R[7] = two_s * (j * k + i * r); R[8] = 1 - two_s * (i * i + j * j);
-}
-
 struct Proj {
     double Xc[3];     // camera-frame point (unclamped)
     double proj[2];   // project_apply output (z clamped at 0.1, transforms.py:47-63)

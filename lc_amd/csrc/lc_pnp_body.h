@@ -195,8 +195,6 @@ struct RawPoint {
     float2 u;
     float a, b, c;
 };
-// torch.nan_to_num with its defaults: NaN -> 0, +-inf -> +-FLT_MAX (cer_solver.py:29-31 applies it to every input when asked to)
-__device__ __forceinline__ float nan_to_num(float f) { return f != f ? 0.f : fminf(fmaxf(f, -FLT_MAX), FLT_MAX); }
 
 // OPTS: the instantiation that honours PnpParams::options / weight_mask (input filtering and weight forms of the callers, done at
 // the load instead of by separate element-wise launches); the plain instantiation does not even test the fields

@@ -12,19 +12,23 @@
 //   Wave 0 then holds the 6x6 matrix one entry per lane: Gauss-Jordan sweeps whose pivots are the squared Cholesky diagonal (the SPD
 //   test of safe_cholesky), the inverse, 24 / 16 lanes with one box-corner Jacobian row each, the mean.
 //
-// Self-contained on purpose: the library's source hash covers this directory and its header only.
+// The in-tile tree is lc::wave_reduce_scatter16<32> of ../shared/lc_shared.h, the one copy the hot-path library's sums use as well
+// (with tri6, shfl_f64, nan_to_num and quat_matrix); nothing else of lc_amd/csrc is included.  The library's source hash covers this
+// directory, its header and that shared header (lc_amd/build.py: POSECOV.shared).
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
 #include <string>
 
 #include "../../../include/lc_amd_posecov.h"
+#include "../shared/lc_shared.h"
 
 #ifndef LC_AMD_POSECOV_SRC_HASH
 #define LC_AMD_POSECOV_SRC_HASH "unrecorded"
 #endif
 
 namespace {
+
+using namespace lc;
 
 const char kSrcHash[] = "LC_AMD_POSECOV_SRC_HASH:" LC_AMD_POSECOV_SRC_HASH;
 thread_local std::string g_err;
@@ -34,7 +38,6 @@ int fail(int code, std::string msg) {
     return code;
 }
 
-constexpr int kWave = 64;
 constexpr int kTile = 64;  // the canonical tile: 64 consecutive correspondences
 constexpr int kRow = 22;   // doubles per tile partial in LDS (21 sums + 1 pad: the lanes store pairs)
 constexpr int kFixed = 24 + 36 + 24 + 2;  // LDS behind the tile rows: H totals | cov | var | flags
@@ -55,64 +58,6 @@ struct Params {
     int N, options, object_rows, pose_rows;
 };
 
-// ---- cross-lane helpers (gfx950: v_permlane32_swap / v_permlane16_swap, DPP row_mirror / row_half_mirror / quad_perm) ----
-constexpr int kDppQuadXor1 = 0xB1, kDppQuadXor2 = 0x4E, kDppIdentity = 0xE4, kDppRowMirror = 0x140, kDppHalfMirror = 0x141;
-
-template <int CTRL, int BANK_MASK = 0xF>
-__device__ __forceinline__ double dpp_mov_f64(double old, double src) {
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(src), CTRL, 0xF, BANK_MASK, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(src), CTRL, 0xF, BANK_MASK, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double shfl_f64(double v, int src) {
-    const int lo = __shfl(__double2loint(v), src, kWave), hi = __shfl(__double2hiint(v), src, kWave);
-    return __hiloint2double(hi, lo);
-}
-// lower half-wave: two-half sum of a; upper half-wave: two-half sum of b
-__device__ __forceinline__ double swap32_add(double a, double b) {
-    const auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(a), __double2loint(b), false, false);
-    const auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(a), __double2hiint(b), false, false);
-    return __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
-}
-__device__ __forceinline__ double swap16_add(double a, double b) {
-    const auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(a), __double2loint(b), false, false);
-    const auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(a), __double2hiint(b), false, false);
-    return __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
-}
-template <int CTRL, int BANK_UP>
-__device__ __forceinline__ double dpp_exchange_add(double lo, double hi) {
-    constexpr int BANK_DOWN = 0xF & ~BANK_UP;
-    const double keep = dpp_mov_f64<kDppIdentity, BANK_UP>(lo, hi);
-    double recv = dpp_mov_f64<CTRL, BANK_UP>(lo, hi);
-    recv = dpp_mov_f64<CTRL, BANK_DOWN>(recv, lo);
-    return keep + recv;
-}
-// Reduce-scatter of 32 doubles across the wave, the in-tile tree: afterwards lane l holds in v[0], v[1] the sums over all 64 lanes of
-// the entries base, base + 1 with base = 2 (8 b5 + 4 b4 + 2 b3 + b2), b_i = bit i of l (every lane of a quad holds the same pair).
-__device__ __forceinline__ void tile_reduce32(double (&v)[32]) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v[i] = swap32_add(v[i], v[i + 16]);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = swap16_add(v[i], v[i + 8]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = dpp_exchange_add<kDppRowMirror, 0xC>(v[i], v[i + 4]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) v[i] = dpp_exchange_add<kDppHalfMirror, 0xA>(v[i], v[i + 2]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        v[i] += dpp_mov_f64<kDppQuadXor2>(v[i], v[i]);
-        v[i] += dpp_mov_f64<kDppQuadXor1>(v[i], v[i]);
-    }
-}
-__device__ __forceinline__ int tile_reduce_base(int lane) {
-    return 2 * (((lane >> 5) & 1) * 8 + ((lane >> 4) & 1) * 4 + ((lane >> 3) & 1) * 2 + ((lane >> 2) & 1));
-}
-
-__host__ __device__ constexpr int tri6(int i, int j) { return i * 6 - (i * (i - 1)) / 2 + (j - i); }
-
-// torch.nan_to_num with its defaults: NaN -> 0, +-inf -> +-FLT_MAX
-__device__ __forceinline__ float nan_to_num(float f) { return f != f ? 0.f : fminf(fmaxf(f, -FLT_MAX), FLT_MAX); }
-
 struct PoseConst {
     double K[9];
     double R[9];   // the matrix the reference uses (two_s = 2/|q|, rotation_conversions.py:52)
@@ -120,13 +65,6 @@ struct PoseConst {
     double rho;
     double t[3];
 };
-
-__device__ __forceinline__ void quat_matrix(const double q[4], double two_s, double R[9]) {
-    const double r = q[0], i = q[1], j = q[2], k = q[3];
-    R[0] = 1 - two_s * (j * j + k * k); R[1] = two_s * (i * j - k * r); R[2] = two_s * (i * k + j * r);
-    R[3] = two_s * (i * j + k * r); R[4] = 1 - two_s * (i * i + k * k); R[5] = two_s * (j * k - i * r);
-    R[6] = two_s * (i * k - j * r); R[7] = two_s * (j * k + i * r); R[8] = 1 - two_s * (i * i + j * j);
-}
 
 // One correspondence: acc[tri6(i, j)] = sum_c w_c (J_c[i] J_c[j] + r_c Hess(r_c)[i][j]), i <= j.
 // residual_with_jac6d (pnp_auto.py:13-56) at delta = 0 and the jacfwd of r * dr (pnp_auto.py:59-83) in closed form: the truncated
@@ -248,8 +186,8 @@ __global__ __launch_bounds__(kWave* NW) void lc_pose_cov_kernel(const Params p) 
             const double w[2] = {fin(w0), fin(w1)};
             point_hessian(pc, X, u, w, acc);
         }
-        tile_reduce32(acc);
-        const int bs = tile_reduce_base(lane);
+        wave_reduce_scatter16<32>(acc, lane);  // the in-tile tree: every lane of a quad ends with the sums base, base + 1 in acc[0], acc[1]
+        const int bs = scatter16_base(lane, 2);
         if ((lane & 3) == 0 && bs < kRow) {
             part[t * kRow + bs] = acc[0];
             part[t * kRow + bs + 1] = acc[1];

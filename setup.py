@@ -38,7 +38,7 @@ setup(
     version="0.1.0",
     description="MI355X-native hot path of fulliu/lc: linear-covariance pose loss, weighted PnP, keypoint head (HIP, gfx950)",
     packages=find_packages(include=["lc_amd", "lc_amd.*"]),
-    package_data={"lc_amd": ["_C/*.so", "csrc/*.hip", "csrc/*.h"]},
+    package_data={"lc_amd": ["_C/*.so", "csrc/*.hip", "csrc/*.h", "csrc/shared/*.h"]},
     data_files=[("include", ["include/lc_amd.h"])],
     python_requires=">=3.10",
     install_requires=["torch", "numpy"],

@@ -423,3 +423,29 @@ def test_training_shape_fixtures_span_the_warm_up_ramp_and_the_reference_shapes(
             assert len(set(mn)) == len(mn) and min(mn) > 0
         else:
             assert tuple(out["pts2d"].shape) == (256, 64, 2) and z["s0_grad_pts2d"].shape == (256, 64, 2)
+
+
+@pytest.mark.parametrize("name", ["main", "crop"])
+def test_shared_loader_refuses_what_it_cannot_rebuild(name, tmp_path, monkeypatch):
+    """The refusal branches of the one loader behind every module's load(), without a compiler run and without a dlopen: a library built
+    from other sources on a box without hipcc, and a missing library where building is not wanted.  Two targets: the messages name the
+    paths and the hashes of the target they were given."""
+    from lc_amd import _lib, build
+
+    target = next(t for t in build.all_targets() if t.name == name)._replace(so_path=str(tmp_path / f"lib_{name}.so"))
+    monkeypatch.setattr(build, "hipcc_available", lambda: False)
+    monkeypatch.setattr(build, "build", lambda *a, **k: pytest.fail("the loader must not try to build here"))
+    monkeypatch.delenv("LC_AMD_ALLOW_STALE", raising=False)
+    with pytest.raises(RuntimeError) as e:  # missing, and the caller does not want a build
+        _lib.load_target(target, {}, build_if_missing=False)
+    assert str(e.value) == f"lc_amd: {target.so_path} is missing or stale; run `python __graft_entry__.py build`"
+    open(target.so_path, "wb").write(b"\x7fELF no marker in here")
+    for build_if_missing in (True, False):  # there, built from other sources (no hash inside), and no compiler to rebuild it with
+        with pytest.raises(RuntimeError) as e:
+            _lib.load_target(target, {}, build_if_missing=build_if_missing)
+        msg = str(e.value)
+        assert msg.startswith(f"lc_amd: {target.so_path} was built from other sources than the ones next to it (embedded hash None, "
+                              f"sources {build.source_hash(target)}) and hipcc is not available")
+        assert msg.endswith("set LC_AMD_ALLOW_STALE=1 to load it as it is")
+    others = {build.source_hash(t) for t in build.all_targets() if t.name != name}
+    assert not any(h in msg for h in others)

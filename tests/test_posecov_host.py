@@ -37,11 +37,54 @@ def test_embedded_source_hash_and_separate_sources():
     lib = posecov.load()
     assert lib.lc_amd_posecov_source_hash().decode() == build.source_hash(build.POSECOV) == build.embedded_hash(build.POSECOV.so_path, build.POSECOV.hash_marker)
     assert build.sources(build.POSECOV) == [os.path.join(build.CSRC, "posecov", "lc_pose_cov.hip")]
-    assert not any("posecov" in s for s in build.sources()) and not any("posecov" in s for s in build._deps())
-    assert len({build.source_hash(t) for t in build.TARGETS}) == 3 and build.TARGETS == (build.MAIN, build.OPTIM, build.POSECOV)
-    # self-contained translation unit: nothing of lc_amd/csrc is included, so the hash (this directory + the header) sees every edit
-    src = open(build.sources(build.POSECOV)[0]).read()
-    assert re.findall(r'#include "([^"]+)"', src) == ["../../../include/lc_amd_posecov.h"]
+    for t in (t for t in build.all_targets() if t is not build.POSECOV):  # no other library sees this directory or header
+        assert not any("posecov" in os.path.relpath(s, ROOT) for s in build._deps(t))
+    assert build.all_targets() == (build.MAIN, build.OPTIM, build.POSECOV, build.RENDER, build.CROP)
+    assert len({build.source_hash(t) for t in build.all_targets()}) == 5
+
+
+def _quoted_includes(path):
+    return [os.path.normpath(os.path.join(os.path.dirname(path), inc)) for inc in re.findall(r'#include "([^"]+)"', open(path).read())]
+
+
+def test_every_library_hashes_every_file_it_includes(tmp_path, monkeypatch):
+    """A library's hash sees every edit that can change it: whatever its .hip and .h files include with quotes, followed through the
+    included files, is one of the files the hash is taken over; the shared header belongs to the two libraries that include it."""
+    import shutil
+
+    from lc_amd import build
+
+    for t in build.all_targets():
+        deps = {os.path.normpath(d) for d in build._deps(t)}
+        assert all(os.path.exists(d) for d in deps), t.name
+        seen, todo = set(), sorted(deps)
+        while todo:
+            f = todo.pop()
+            if f in seen:
+                continue
+            seen.add(f)
+            assert f in deps, f"{t.name}: {f} is included but not hashed"
+            todo += _quoted_includes(f)
+    shared = os.path.join(build.CSRC, "shared", "lc_shared.h")
+    assert [t for t in build.all_targets() if shared in build._deps(t)] == [build.MAIN, build.POSECOV]
+    assert shared in _quoted_includes(os.path.join(build.CSRC, "lc_common.h")) and shared in _quoted_includes(build.sources(build.POSECOV)[0])
+
+    # one more byte in the shared header of a COPY of the sources: exactly those two hashes change
+    pkg = tmp_path / "lc_amd"
+    shutil.copytree(build.CSRC, pkg / "csrc")
+    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "include")
+    monkeypatch.setattr(build, "PKG", str(pkg))  # where _deps looks for include/
+
+    def moved(path):
+        return str(pkg / os.path.relpath(path, os.path.dirname(build.CSRC)))
+
+    copies = [t._replace(src_dir=moved(t.src_dir), shared=tuple(moved(s) for s in t.shared)) for t in build.all_targets()]
+    before = [build.source_hash(t) for t in copies]
+    assert before == [build.source_hash(t) for t in build.all_targets()]  # (names and contents: the copy hashes like the tree)
+    with open(moved(shared), "ab") as f:
+        f.write(b"\n")
+    after = [build.source_hash(t) for t in copies]
+    assert [t.name for t, x, y in zip(copies, before, after) if x != y] == ["main", "posecov"]
 
 
 def test_entry_point_checks_its_arguments():

@@ -42,12 +42,13 @@ def test_embedded_source_hash_and_separate_sources():
     lib = render.load()
     assert lib.lc_amd_render_source_hash().decode() == build.source_hash(build.RENDER) == build.embedded_hash(build.RENDER.so_path, build.RENDER.hash_marker)
     assert build.sources(build.RENDER) == [os.path.join(build.CSRC, "render", "lc_render.hip")]
-    # the three existing libraries: the same tuple, the same sources, none of them sees the new directory or header
-    assert build.TARGETS == (build.MAIN, build.OPTIM, build.POSECOV) and build.EXTRA_TARGETS == (build.RENDER,)
-    for t in build.TARGETS:
+    # the one registry: the five libraries in build order, five different hashes; no other library sees this directory or header
+    assert build.all_targets() == (build.MAIN, build.OPTIM, build.POSECOV, build.RENDER, build.CROP)
+    others = [t for t in build.all_targets() if t is not build.RENDER]
+    for t in others:
         assert not any("render" in os.path.basename(s) or os.sep + "render" + os.sep in s for s in build._deps(t))
-    assert len({build.source_hash(t) for t in build.TARGETS + build.EXTRA_TARGETS}) == 4
-    for t in build.TARGETS:  # their libraries, as built, still carry the hash of their sources
+    assert len({build.source_hash(t) for t in build.all_targets()}) == 5
+    for t in others:  # their libraries, as built, still carry the hash of their sources
         assert build.embedded_hash(t.so_path, t.hash_marker) in (None, build.source_hash(t))
     src = open(build.sources(build.RENDER)[0]).read()
     assert re.findall(r'#include "([^"]+)"', src) == ["../../../include/lc_amd_render.h"]
