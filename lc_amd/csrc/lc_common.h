@@ -135,30 +135,32 @@ __device__ __forceinline__ void block_sum_bcast_lds(double (&v)[K], double* lds,
 template <int K, int NW>
 __device__ __forceinline__ double* block_sum_totals(double* lds) { return lds + K * (68 * NW); }
 
+// sum of one 32-double segment of a row (sixteen 16-byte reads): the order every form of the LDS block sum adds a segment in
+__device__ __forceinline__ double block_sum_segment(const double2* row) {
+    double2 a[8];  // two batches of eight 16-byte reads: keeps the register peak (and so the occupancy) down
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = row[i];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const double2 t = row[8 + i];
+        a[i].x += t.x;
+        a[i].y += t.y;
+    }
+#pragma unroll
+    for (int st = 4; st >= 1; st >>= 1) {
+#pragma unroll
+        for (int i = 0; i < st; ++i) { a[i].x += a[i + st].x; a[i].y += a[i + st].y; }
+    }
+    return a[0].x + a[0].y;
+}
+
 template <int K, int NW>
 __device__ __forceinline__ void block_sum_reduce(double* lds, int tid) {
     static_assert(K <= 32 && (NW == 1 || NW == 4), "unsupported shape");
     constexpr int LD = 68 * NW, S = 2 * NW;
     block_sum_sync<NW>();
     double s = 0;
-    if (tid < K * S) {
-        const double2* row = reinterpret_cast<const double2*>(lds + (tid / S) * LD + 34 * (tid % S));
-        double2 a[8];  // two batches of eight 16-byte reads: keeps the register peak (and so the occupancy) down
-#pragma unroll
-        for (int i = 0; i < 8; ++i) a[i] = row[i];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const double2 t = row[8 + i];
-            a[i].x += t.x;
-            a[i].y += t.y;
-        }
-#pragma unroll
-        for (int st = 4; st >= 1; st >>= 1) {
-#pragma unroll
-            for (int i = 0; i < st; ++i) { a[i].x += a[i + st].x; a[i].y += a[i + st].y; }
-        }
-        s = a[0].x + a[0].y;
-    }
+    if (tid < K * S) s = block_sum_segment(reinterpret_cast<const double2*>(lds + (tid / S) * LD + 34 * (tid % S)));
     s += dpp_mov_f64<kDppQuadXor1>(s, s);
     if constexpr (NW == 4) {
         s += dpp_mov_f64<kDppQuadXor2>(s, s);
@@ -173,6 +175,31 @@ template <int K, int NW>
 __device__ __forceinline__ void block_sum_close(double (&v)[K], double* lds, int tid) {
     block_sum_reduce<K, NW>(lds, tid);
     const double* tot = block_sum_totals<K, NW>(lds);
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = tot[k];
+}
+
+// The one-wave sum (NW = 1) played by a TEAM of two wavefronts that both hold all 64 values of every entry (lane = point in both:
+// the pose unit's latency build, where half the SIMDs idle next to a wave that is bound by instruction issue).  Wave W produces and
+// stores only the entries k with k % 2 == W -- block_sum_put<1> into the slots of the one-wave form -- and sums them itself: lane
+// l < K takes segment l % 2 of entry 2 (l / 2) + W with the instruction sequence of block_sum_reduce<K, 1>, so every total has the
+// one-wave form's bits.  A wave's rows are written and read by that wave alone (DS operations of a wave execute in program order: no
+// barrier between its stores and its reads); the K / 2 totals of each wave meet in one of TWO rows of totals behind the slots, then
+// ONE workgroup barrier, then every thread of both waves reads all K.  The rows alternate by `phase` (toggled by the call, as in
+// block_sum_waves4): a wave still reading the totals of sum e is not overwritten by sum e + 1, and whoever writes sum e + 2 has
+// passed the barrier of e + 1, which the other wave only reaches with its reads of e done.  lds: sum_team2_lds_doubles(K) doubles.
+constexpr int sum_team2_lds_doubles(int K) { return K * 68 + 2 * K; }
+template <int K, int W>
+__device__ __forceinline__ void block_sum_team2(double (&v)[K], double* lds, int lane, int& phase) {
+    static_assert(K % 2 == 0 && K <= 32 && (W == 0 || W == 1), "an even number of entries dealt to two waves");
+    wave_sync();  // this wave's stores are in its LDS queue
+    double s = 0;
+    if (lane < K) s = block_sum_segment(reinterpret_cast<const double2*>(lds + (2 * (lane / 2) + W) * 68 + 34 * (lane % 2)));
+    s += dpp_mov_f64<kDppQuadXor1>(s, s);
+    double* tot = lds + K * 68 + K * phase;
+    phase ^= 1;
+    if (lane < K && (lane % 2) == 0) tot[lane + W] = s;  // entry 2 (lane / 2) + W
+    __syncthreads();
 #pragma unroll
     for (int k = 0; k < K; ++k) v[k] = tot[k];
 }

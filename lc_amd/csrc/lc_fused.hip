@@ -14,7 +14,7 @@ int launch_pose_unit(const LossParams& lp, const PnpParams& pp, hipStream_t stre
     if (blocks > kLatencyGridMax)
         hipLaunchKernelGGL(lc_pose_unit_kernel<LC_BIG_WPS>, dim3(blocks), dim3(64), 0, stream, lp, pp);
     else
-        return launch_pose_unit_latency(lp, pp, blocks, stream);
+        return launch_pose_unit_latency(lp, pp, stream);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

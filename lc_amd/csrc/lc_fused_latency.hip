@@ -1,4 +1,5 @@
-// The metric's launch: the pose-unit kernel for grids of at most kLatencyGridMax one-wave workgroups (B = 256: 512 of them), in a
+// The metric's launch: the pose-unit kernel for at most kLatencyGridMax poses + samples (B = 256: 256 two-wave solve workgroups and 128
+// loss workgroups of two samples each, lc_fused_kernel.h; with -DLC_PNP_TEAM2=0, or beyond 1024 waves of that form, one-wave workgroups), in a
 // translation unit of its own because it is compiled with the max-ILP machine scheduler (lc_amd/build.py: PER_FILE_FLAGS; measurements
 // and why only here: lc_pnp_latency.hip).  The solve is the critical path of the launch; the loss half, 4 % slower under this
 // scheduler when run alone, still finishes well inside it.
@@ -6,8 +7,13 @@
 
 namespace lc {
 
-int launch_pose_unit_latency(const LossParams& lp, const PnpParams& pp, int blocks, hipStream_t stream) {
-    hipLaunchKernelGGL(lc_pose_unit_kernel<1>, dim3(blocks), dim3(64), 0, stream, lp, pp);
+int launch_pose_unit_latency(const LossParams& lp, const PnpParams& pp, hipStream_t stream) {
+    const int samples = lp.B > 0 ? lp.B : 0, poses = pp.B > 0 ? pp.B : 0;
+#if LC_PNP_TEAM2
+    if (2 * poses + samples <= kLatencyGridMax) hipLaunchKernelGGL((lc_pose_unit_kernel<1, true>), dim3(poses + (samples + 1) / 2), dim3(128), 0, stream, lp, pp);
+    else
+#endif
+    hipLaunchKernelGGL(lc_pose_unit_kernel<1>, dim3(poses + samples), dim3(64), 0, stream, lp, pp);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

@@ -36,9 +36,11 @@
 namespace lc {
 namespace loss {
 
-struct LossShared {
-    double red[16][48];   // cross-wave partials of the 48-value reduction
-    double small[16][4];  // cross-wave partials of the small reductions
+// NWMAX: wavefronts that may share the sample (1: the pose unit's latency build parks two samples, one per wavefront, in a workgroup's LDS)
+template <int NWMAX>
+struct LossSharedN {
+    double red[NWMAX][48];   // cross-wave partials of the 48-value reduction
+    double small[NWMAX][4];  // cross-wave partials of the small reductions
     double A0[36];          // S = H^-1
     double sv[6];           // S*v
     double2 HM[24 * 6] __attribute__((aligned(16)));  // per bbox-Jacobian row j: pairs (h_j[a], m_j[a]), h_j = S g_j, m_j = S Mc h_j
@@ -46,6 +48,7 @@ struct LossShared {
     double Hbar[36], Psi[36], mu[6];
     int bad[4];  // [0],[1]: a non-positive diagonal in loss_cov_3d (P, C); [2]: H not SPD
 };
+using LossShared = LossSharedN<16>;
 
 // the one-workgroup loop form adds the per-tile partial rows of the canonical summation order
 struct LossSharedLoop : LossShared {
@@ -314,17 +317,20 @@ __device__ __forceinline__ Pt to_pt(const RawPt& r) {
 //   A range of at most four tiles per wave is loaded ONCE (raw floats + clamped errors in registers) and serves all passes.
 // COV2D: covariance of the projected bbox corners (cov_mixed.py:125-127) instead of the 3D ones (every reference call site).
 // SH: LossShared (REG) or LossSharedLoop (!REG)
+// WAVE (REG, N <= 64): the sample belongs to ONE wavefront of a workgroup that holds several samples (SH = LossSharedN<1>, one per wavefront):
+// the wave is the sample's whole "workgroup" -- its lanes are the thread indices, and it meets no workgroup barrier
 template <bool C, class A, class B>
 __device__ __forceinline__ auto& pick_ref(A& a, B& b) {
     if constexpr (C) return a;
     else return b;
 }
 
-template <bool REG, bool COV2D = false, bool GRID = false, typename SH = LossShared>
+template <bool REG, bool COV2D = false, bool GRID = false, typename SH = LossShared, bool WAVE = false>
 __device__ __forceinline__ void sample(const LossParams& p, const int b, SH& sh, GridCtx* gc = nullptr) {
     static_assert(!GRID || !REG, "the tiled form is a walk form");
+    static_assert(!WAVE || (REG && !LC_WAVE_SYNC), "a wave on its own has one correspondence per lane and no barrier");
     constexpr bool WALK = !REG;
-    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int tid = WAVE ? (int)(threadIdx.x & 63u) : (int)threadIdx.x, nthr = WAVE ? kWave : (int)blockDim.x;
     const int lane = tid & 63, wave = tid >> 6, nw = nthr >> 6;
     const int N = p.N;
     const size_t base = (size_t)b * N;

@@ -1,4 +1,5 @@
-// Device body of the batched weighted-PnP solve: one wavefront runs one pose's whole Levenberg-Marquardt solve.
+// Device body of the batched weighted-PnP solve: one wavefront runs one pose's whole Levenberg-Marquardt solve (small grids of the plain
+// solve: a TEAM of two wavefronts that split the 28 sums of an evaluation between them, see solve_pose).
 // Included by lc_pnp.hip (stand-alone kernel) and lc_fused.hip (loss + PnP in one launch).
 //
 // Replaces lib/pnp/cxx/ceres.cpp:72-145 (pnp_ceres_f32 -> ceres::Solve, DENSE_QR, autodiff Jets) and its OpenMP
@@ -48,6 +49,9 @@
 #ifndef LC_WIDE_REG_SUM_REGS
 #define LC_WIDE_REG_SUM_REGS 1  // A/B switch: the four-wave register block sum also on the one-correspondence-per-thread path (N <= 256: 12.4 -> 11.6 us at 64 x 256; 0 = sums streamed through LDS)
 #endif
+#ifndef LC_PNP_TEAM2
+#define LC_PNP_TEAM2 (!LC_WAVE_SYNC)  // A/B switch: the latency builds of the one-correspondence-per-lane solve (plain instantiations: lc_pnp_latency.hip, lc_fused_kernel.h) run TWO wavefronts per pose that share the products and the block sum (TEAM below); 0 = one wavefront per pose (also what the LC_WAVE_SYNC diagnostic build gets)
+#endif
 #ifndef LC_PNP_STREAM_SUM
 #define LC_PNP_STREAM_SUM 1  // A/B switch of the streamed block sum (scripts/ubench/pnp_ab.py); 1 in the shipped library
 #endif
@@ -57,6 +61,7 @@ namespace pnp {
 
 template <int NW>
 constexpr int kPnpLdsDoubles = sum_bcast_lds_doubles<NW>(28);  // block_sum_bcast_lds<28, NW>
+constexpr int kPnpTeamLdsDoubles = sum_team2_lds_doubles(28);  // block_sum_team2<28>: the one-wave slots and a second row of totals
 
 struct Point {
     double X[3];
@@ -99,7 +104,8 @@ __device__ __forceinline__ void make_rot(const double aa[3], Rot& o) {
 // (columns of J pre-multiplied by the Jacobi scaling sc: acc holds Js^T Js and Js^T r directly)
 // FIRST: acc is written (not added to) -- saves zero-filling 32 accumulators and one add per entry when a lane owns one point.
 // STREAM: (FIRST only) every finished entry goes straight to its LDS slot of the block sum instead of into acc[]
-template <bool FIRST, bool STREAM = false, int NW = 1>
+// PAR (STREAM only): 0 / 1 = only the entries of that parity are formed and stored (the two waves of a team, block_sum_team2); -1 = all
+template <bool FIRST, bool STREAM = false, int NW = 1, int PAR = -1>
 __device__ __forceinline__ void accumulate_point(const Point& pt, const Rot& rt, const double t[3], const double k[6],
                                                  const double (&sc)[6], double (&acc)[28], double* lds = nullptr, int pos = 0) {
     double rx[3], q[3];  // R X and R X + t
@@ -133,21 +139,29 @@ __device__ __forceinline__ void accumulate_point(const Point& pt, const Rot& rt,
 #pragma unroll
         for (int m = 0; m < 3; ++m) J[rr][3 + m] *= sc[3 + m];
     }
+    static_assert(PAR < 0 || STREAM, "entries are dealt by parity where they go to their LDS slots");
+    constexpr auto mine = [](int k) { return PAR < 0 || (k & 1) == PAR; };  // (folds once the loops are unrolled)
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
 #pragma unroll
         for (int j = i; j < 6; ++j) {
-            const double v = __builtin_fma(J[0][i], J[0][j], J[1][i] * J[1][j]);
-            if constexpr (STREAM) block_sum_put<NW>(lds, pos, tri6(i, j), v);
-            else acc[tri6(i, j)] = FIRST ? v : acc[tri6(i, j)] + v;
+            if (mine(tri6(i, j))) {
+                const double v = __builtin_fma(J[0][i], J[0][j], J[1][i] * J[1][j]);
+                if constexpr (STREAM) block_sum_put<NW>(lds, pos, tri6(i, j), v);
+                else acc[tri6(i, j)] = FIRST ? v : acc[tri6(i, j)] + v;
+            }
         }
-        const double gi = __builtin_fma(J[0][i], r[0], J[1][i] * r[1]);
-        if constexpr (STREAM) block_sum_put<NW>(lds, pos, 21 + i, gi);
-        else acc[21 + i] = FIRST ? gi : acc[21 + i] + gi;
+        if (mine(21 + i)) {
+            const double gi = __builtin_fma(J[0][i], r[0], J[1][i] * r[1]);
+            if constexpr (STREAM) block_sum_put<NW>(lds, pos, 21 + i, gi);
+            else acc[21 + i] = FIRST ? gi : acc[21 + i] + gi;
+        }
     }
-    const double ss = __builtin_fma(r[0], r[0], r[1] * r[1]);
-    if constexpr (STREAM) block_sum_put<NW>(lds, pos, 27, ss);
-    else acc[27] = FIRST ? ss : acc[27] + ss;
+    if (mine(27)) {
+        const double ss = __builtin_fma(r[0], r[0], r[1] * r[1]);
+        if constexpr (STREAM) block_sum_put<NW>(lds, pos, 27, ss);
+        else acc[27] = FIRST ? ss : acc[27] + ss;
+    }
 }
 
 // solve (A + diag(dg)) y = rhs for symmetric A (packed upper 21) by LDL^T; false if a pivot is not positive/finite
@@ -268,12 +282,19 @@ __device__ __forceinline__ double norm6(const double (&v)[6]) {
 // the block sum runs across the G workgroups (lc_common.h: block_sum_split), everything else is replicated; part 0 stores -- status 2 when
 // its wait for another part ran out.  SPLIT = 2 (NW = 4, PPT = 0): ONE workgroup plays the sx->G parts in turn (the rescue launch of a pose
 // of status 2: block_sum_parts_serial) -- per thread the same correspondences in the same order, every sum in the same order: the same bits.
-template <bool REG, int NW = 1, bool TRACE = false, bool OPTS = false, int PPT = 0, bool TAIL = false, int SPLIT = 0>
+// TEAM = 0 / 1 (REG, NW = 1; -1 = off): wave TEAM of a 128-thread workgroup whose TWO wavefronts solve ONE pose (`lane` = lane of the wave, bc:
+// kPnpTeamLdsDoubles).  Both waves hold all correspondences and run the whole solve -- load, quaternion -> angle-axis, make_rot, geometry and
+// Jacobian rows, Jacobi scaling, LDL^T, the schedule: the same expressions on the same values, so they take every branch together -- but each
+// forms, stores and sums only the 14 of the 28 entries J^T J | J^T r | r^T r of its parity (lc_common.h: block_sum_team2, one workgroup
+// barrier per evaluation; every break / continue / return is taken by both waves, so their barrier counts agree; the n < 3 exit comes before
+// the first).  Every total is summed in the one-wave form's order: the same bits.  Wave 0 stores (the caller passes store = false to wave 1).
+template <bool REG, int NW = 1, bool TRACE = false, bool OPTS = false, int PPT = 0, bool TAIL = false, int SPLIT = 0, int TEAM = -1>
 __device__ __forceinline__ void solve_pose(const PnpParams& p, int b, int lane, double* bc, bool store = true, float* handoff = nullptr,
                                            const float* start_override = nullptr, [[maybe_unused]] SplitSum* sx = nullptr) {
     constexpr int kThreads = kWave * NW;  // `lane` is the thread index within the workgroup
     static_assert(SPLIT != 1 || (NW == 4 && !REG && PPT > 0 && !TRACE), "the split form is the four-wave cached-prefix solve");
     static_assert(SPLIT != 2 || (NW == 4 && !REG && PPT == 0 && !TRACE), "the rescue form walks memory, part by part");
+    static_assert(TEAM < 0 || (TEAM <= 1 && REG && NW == 1 && !TRACE && SPLIT == 0), "the team form is the one-correspondence-per-lane solve");
     const int slot = SPLIT == 1 ? lane + kThreads * sx->part : lane;  // first correspondence of this thread, and the distance to its next
     const int stride = SPLIT == 1 ? kThreads * sx->G : kThreads;
 #ifdef LC_TRACE_CLOCK
@@ -352,7 +373,7 @@ __device__ __forceinline__ void solve_pose(const PnpParams& p, int b, int lane, 
         if (!active) { rp.a = 0.0; rp.b = 0.0; rp.c = 0.0; }
     }
 
-    [[maybe_unused]] int sum_phase = 0;  // block_sum_waves4: which of its two rows of totals the next sum writes
+    [[maybe_unused]] int sum_phase = 0;  // block_sum_waves4 / block_sum_team2: which of its two rows of totals the next sum writes
     // full evaluation at xe with column scaling sc: H = Js^T Js (21), g = Js^T r (6), cost; false when anything is non-finite
     auto evaluate = [&](const double (&xe)[6], const double (&sc)[6], double (&H)[21], double (&g)[6], double& cost) -> bool {
         LC_PSTAMP(1);
@@ -361,7 +382,13 @@ __device__ __forceinline__ void solve_pose(const PnpParams& p, int b, int lane, 
         LC_PSTAMP(2);
         const double t[3] = {xe[3], xe[4], xe[5]};
         double acc[28];
-        if constexpr (REG && LC_PNP_STREAM_SUM && !(NW == 4 && LC_WIDE_REG_SUM_REGS)) {
+        if constexpr (TEAM >= 0) {
+            // this wave's half of the 28 partial sums goes to LDS as it is produced; the sibling wave forms the other half
+            const int pos = block_sum_open<1>(lane);
+            accumulate_point<true, true, 1, TEAM>(rp, rt, t, cam, sc, acc, bc, pos);
+            LC_PSTAMP(3);
+            block_sum_team2<28, TEAM>(acc, bc, lane, sum_phase);
+        } else if constexpr (REG && LC_PNP_STREAM_SUM && !(NW == 4 && LC_WIDE_REG_SUM_REGS)) {
             // lanes beyond n hold zero-weight copies (exact zeros); the 28 partial sums go to LDS as they are produced
             const int pos = block_sum_open<NW>(lane);
             accumulate_point<true, true, NW>(rp, rt, t, cam, sc, acc, bc, pos);
@@ -544,7 +571,7 @@ __device__ __forceinline__ void solve_pose(const PnpParams& p, int b, int lane, 
     }
     LC_PSTAMP(1);
 #ifdef LC_STAMPS
-    if (lane == 0 && p.iters) {
+    if (lane == 0 && store && p.iters) {
         unsigned long long* o = reinterpret_cast<unsigned long long*>(p.iters) + 8 * (size_t)b;
         for (int i = 0; i < 6; ++i) o[i] = pst_[i];
         o[6] = iter;

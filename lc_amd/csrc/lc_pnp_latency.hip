@@ -1,4 +1,4 @@
-// The latency build of the one-wave-per-pose solve (N <= 64, grids of at most kLatencyGridMax workgroups: the metric's B = 256), in a
+// The latency build of the one-correspondence-per-lane solve (N <= 64, grids of at most kLatencyGridMax poses: the metric's B = 256), in a
 // translation unit of its own because it is compiled with another machine scheduler than the rest of the library:
 // `-mllvm -amdgpu-sched-strategy=max-ilp` (lc_amd/build.py: PER_FILE_FLAGS).  A lone wave per SIMD has nobody to hide its latencies
 // behind; the max-ILP strategy orders the ~860 instructions of an LM iteration for the shortest dependent chains instead of for
@@ -29,6 +29,9 @@ int launch_pnp_lm_chain_latency(const PnpParams& a, const PnpParams& b, int seco
 
 int launch_pnp_lm_latency(const PnpParams& p, hipStream_t stream) {
     if (p.options || p.weight_mask || p.pose_mod > 0) hipLaunchKernelGGL((lc_pnp_lm_kernel<true, 1, true>), dim3(p.B), dim3(64), 0, stream, p);
+#if LC_PNP_TEAM2
+    else if (2 * p.B <= kLatencyGridMax) hipLaunchKernelGGL((lc_pnp_lm_kernel<true, 1, false, true>), dim3(p.B), dim3(128), 0, stream, p);  // two wavefronts per pose while each gets a SIMD of its own
+#endif
     else hipLaunchKernelGGL((lc_pnp_lm_kernel<true, 1>), dim3(p.B), dim3(64), 0, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
