@@ -416,11 +416,34 @@ __device__ __forceinline__ double horner_step(double p, double z, double c) {
 // sin and cos of a rotation angle 0 <= x <~ 8 (angle-axis norms; the LM keeps them within a few pi): Cody-Waite reduction
 // by pi/2 into [-pi/4, pi/4] and the fdlibm minimax polynomials (|error| < 1 ulp on that interval).  About a third of the
 // instructions of the general sincos(), whose Payne-Hanek path for huge arguments is never needed here.
-__device__ __forceinline__ void sincos_small(double x, double& s, double& c) {
+// LC_SINCOS_FALLBACK_CALL (set by the latency translation units, whose lone wave per SIMD has registers to spare): the general sincos()
+// behind the reduction is a CALL, so that its Payne-Hanek path -- ~190 instructions wherever it is inlined, and sincos_small sits in every
+// evaluation of the LM loop -- exists once per code object and away from the loop's code.  The occupancy builds keep it inline: a call
+// costs them registers around it (and a stack), and their several waves per SIMD hide an instruction-cache miss.
+#ifndef LC_SINCOS_FALLBACK_CALL
+#define LC_SINCOS_FALLBACK_CALL 0
+#endif
+#if LC_SINCOS_FALLBACK_CALL
+static __device__ __attribute__((noinline, cold)) double2 sincos_full_range(double x) {
+    double s, c;
+    sincos(x, &s, &c);
+    return make_double2(s, c);
+}
+#endif
+static __device__ __forceinline__ void sincos_small(double x, double& s, double& c) {
+#if LC_SINCOS_FALLBACK_CALL
+    if (__builtin_expect(!(x < 1.0e4), 0)) {  // wave-uniform and never taken in practice: keep full-range correctness anyway
+        const double2 sc = sincos_full_range(x);
+        s = sc.x;
+        c = sc.y;
+        return;
+    }
+#else
     if (!(x < 1.0e4)) {  // wave-uniform and never taken in practice: keep full-range correctness anyway
         sincos(x, &s, &c);
         return;
     }
+#endif
     const double kf = __builtin_rint(x * 0.63661977236758134308);  // x * 2/pi
     const int q = (int)kf;
     double r = __builtin_fma(-kf, 1.57079632673412561417e+00, x);   // pi/2 split in three parts (fdlibm pio2_1, _2, _3)

@@ -5,6 +5,10 @@
 // wavefront, each with its own LossSharedN<1> and no workgroup barrier.  At B = 256 that is 512 solve waves + 256 loss waves on the chip's
 // 1024 SIMDs, where the one-wave form leaves half of them idle for the whole launch; it is launched while every wave still gets a SIMD of
 // its own (two per pose + one per sample <= kLatencyGridMax: the kernel needs more than half a SIMD's registers).
+// Code size: the TEAM kernel is two copies of the solve (one per parity) and the loss body, run side by side by the wavefronts of neighbouring
+// compute units that share one 64 KB instruction cache.  The latency build calls the never-taken full-range sincos() instead of inlining it
+// into every evaluation (lc_common.h: LC_SINCOS_FALLBACK_CALL): 42 KB against 51 KB.  Folding the three inlined evaluations of a solve copy
+// into one loop body (35 KB) was measured 10-14 % SLOWER and is not done; counters, timings and both decisions: profiles/icache2/NOTES.md.
 #pragma once
 #include "lc_loss_body.h"
 #include "lc_pnp_body.h"

@@ -3,6 +3,9 @@
 // translation unit of its own because it is compiled with the max-ILP machine scheduler (lc_amd/build.py: PER_FILE_FLAGS; measurements
 // and why only here: lc_pnp_latency.hip).  The solve is the critical path of the launch; the loss half, 4 % slower under this
 // scheduler when run alone, still finishes well inside it.
+#ifndef LC_SINCOS_FALLBACK_CALL
+#define LC_SINCOS_FALLBACK_CALL 1  // the never-taken full-range sincos() out of the LM loop's code (lc_common.h: sincos_small)
+#endif
 #include "lc_fused_kernel.h"
 
 namespace lc {

@@ -5,6 +5,9 @@
 // register pressure: 13.14 -> 12.77 us for the solve, 13.52 -> 13.14 us for the pose unit, same bits (scripts/ubench/pnp_ab.py).
 // At several waves per SIMD the default strategy is the faster one (B = 65 536: 671 vs 680 us), so the large-grid instantiations stay
 // in lc_pnp.hip; the loss kernel alone is 4 % slower under max-ILP and stays out as well.
+#ifndef LC_SINCOS_FALLBACK_CALL
+#define LC_SINCOS_FALLBACK_CALL 1  // the never-taken full-range sincos() out of the LM loop's code (lc_common.h: sincos_small)
+#endif
 #include "lc_pnp_kernels.h"
 
 namespace lc {
