@@ -77,24 +77,15 @@ __device__ __forceinline__ void load_px(const unsigned char* g, bool (&v)[V]) {
 }
 template <int V, typename T>
 __device__ __forceinline__ void store_px(T* o, const float (&v)[V]) {
-    map_store<V>(o, v, V == 4 && LC_NT_GRAD_STORES);  // d_logits: written once, read by the next kernel of the backward pass
+    map_store<V>(o, v, V == 4);  // d_logits: written once, read by the next kernel of the backward pass
 }
 
 // The channels of an axis are requested kChanBatch at a time, every request of a batch before the first use: walked one channel at a time
 // (load, use, load, ...) a wavefront had ONE request in flight, and the decode of 16-bit logits -- half the bytes -- was hardly faster than
 // fp32 (17.0 vs 19.3 us at 64 x 21 x 128 x 128: a chain of 21 memory round trips per thread, not bandwidth).  The kernels request the first
 // batch of all three axes up front.
-#ifndef LC_BITS_GT_PIPELINE
-#define LC_BITS_GT_PIPELINE 1
-#endif
 #ifndef LC_BITS_GT_BATCH
 #define LC_BITS_GT_BATCH 1
-#endif
-#ifndef LC_BITS_FWD_WIDE
-#define LC_BITS_FWD_WIDE 1  // A/B switch: 0 = the generic forward kernel for strided subsets too
-#endif
-#ifndef LC_BITS_BWD_TILES
-#define LC_BITS_BWD_TILES 1  // A/B switch: 0 = the flat backward kernel for strided subsets too
 #endif
 constexpr int kGrayBatch = 8, kGtBatch = LC_BITS_GT_BATCH;  // channels per batch: inference decode / training decode (which also holds the ground-truth bits and the axis state)
 template <int V, int kChanBatch>
@@ -146,7 +137,6 @@ __device__ __forceinline__ void decode_axis_gt(const T* lg, const unsigned char*
             }
         }
     };
-#if LC_BITS_GT_PIPELINE
     // one batch ahead: the next batch is requested before the current one is walked (the last request repeats the axis' last channel)
     ChanBatch<V, kGtBatch> cur = first;
     for (int k0 = 0; k0 < n; k0 += kChanBatch) {
@@ -155,14 +145,6 @@ __device__ __forceinline__ void decode_axis_gt(const T* lg, const unsigned char*
         walk(cur, k0);
         cur = nxt;
     }
-#else
-    walk(first, 0);
-    for (int k0 = kChanBatch; k0 < n; k0 += kChanBatch) {  // more than kChanBatch code bits on the axis
-        ChanBatch<V, kGtBatch> more;
-        load_channels<V>(lg, gt, stride, k0, n, more);
-        walk(more, k0);
-    }
-#endif
 }
 
 // floatbits.py:194-223 for one axis of V pixels
@@ -653,7 +635,7 @@ int launch_bits_decode_gt_fwd(const BitsParams& p_in, hipStream_t stream) {
     if (p_in.B <= 0 || p_in.N <= 0) return 0;
     const BitsParams p = with_dense_stride(p_in);
     const bool vec = (p.logits_bs % 4) == 0 && p.sample == 1 && p.top == 0 && p.left == 0 && p.W % 4 == 0 && map_aligned4(p.logits, p.map_dtype) && aligned16(p.out) && aligned4(p.gt_bits) && aligned4(p.gt_msk);
-    if (LC_BITS_FWD_WIDE && !vec && p.B <= 65535) {  // strided subsets (and odd shapes): every request of a pixel in flight at once
+    if (!vec && p.B <= 65535) {  // strided subsets (and odd shapes): every request of a pixel in flight at once
         LC_MAP_DISPATCH(p.map_dtype, hipLaunchKernelGGL(lc_bits_decode_gt_fwd_wide_kernel<T>, dim3((p.N + kThreads - 1) / kThreads, p.B), dim3(kThreads), 0, stream, p));
         return hipGetLastError() == hipSuccess ? 0 : 2;
     }
@@ -674,7 +656,7 @@ int launch_bits_decode_gt_bwd(const BitsParams& p_in, hipStream_t stream) {
     int tile_rows = 0;
     for (int R = kTileRows; R >= 1 && !tile_rows && per_row > 0 && kThreads % per_row == 0; --R)
         if (((R + p.sample - 1) / p.sample) * Wn * 3 <= kThreads && R * per_row <= kThreads) tile_rows = R;
-    if (LC_BITS_BWD_TILES && (p.sample == 2 || p.sample == 3) && tile_rows > 0 && aligned16(p.d_logits) && p.B <= 65535) {
+    if ((p.sample == 2 || p.sample == 3) && tile_rows > 0 && aligned16(p.d_logits) && p.B <= 65535) {
         BitsParams pt = p;
         pt.tile_groups = (kThreads / per_row) / tile_rows;
         const dim3 grid((p.H + tile_rows - 1) / tile_rows, p.B), block(per_row, kThreads / per_row);

@@ -9,17 +9,10 @@ namespace lc {
 
 // 16-byte store of a write-once stream (a gradient map the kernel never re-reads): non-temporal, so that it does not push the
 // maps the next kernel re-reads out of L2 / Infinity Cache (measured on the keypoint head: profiles/r02/head_policy.txt).
-#ifndef LC_NT_GRAD_STORES
-#define LC_NT_GRAD_STORES 1
-#endif
 typedef float lc_v4f_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void store_stream4(float* q, float a, float b, float c, float d) {
-#if LC_NT_GRAD_STORES
     lc_v4f_t r = {a, b, c, d};
     __builtin_nontemporal_store(r, reinterpret_cast<lc_v4f_t*>(q));
-#else
-    *reinterpret_cast<float4*>(q) = make_float4(a, b, c, d);
-#endif
 }
 
 
@@ -48,26 +41,6 @@ __device__ __forceinline__ double fast_sqrt(double x) {
     return s;
 }
 
-// Sum of K doubles per thread over the 64*NW threads of a workgroup, result in every thread, through LDS.
-// Thread t stores v[k] at lds[k*LD + t + 2*(t/32)] (32-double segments padded by 16 bytes, LD = 68*NW doubles: conflict-free
-// ds_write_b64 and ds_read_b128); thread r < K*S (S = 2*NW segments per row) sums one segment with eight + eight 16-byte
-// reads, the S partial sums of a row meet by DPP (S consecutive, S-aligned lanes), the K totals are re-read by all threads.
-// Measured cheaper than the permlane/DPP reduce-scatter + broadcast for a lone wave (each 64-bit cross-lane exchange costs
-// 25-32 cycles, scripts/ubench/fp64_latency.cpp).  Needs K <= 32, NW in {1, 4} and K*68*NW + K doubles of LDS.
-template <int NW>
-constexpr int sum_bcast_lds_doubles(int K) { return K * 68 * NW + K; }
-
-// The two halves of the sum can be called separately: block_sum_open() (barrier: the previous totals have been read), then the
-// caller stores its K values itself with block_sum_put() AS IT PRODUCES THEM -- the LDS stores of a lone wave drain at about
-// 40 B/clk (MI355X_MICROARCH.md, LDS: one wave gets half the store rate), 360 cycles for 28 doubles x 64 lanes, and issued early they
-// drain behind the arithmetic that produces the later values -- then block_sum_close() for the reduction and the broadcast.
-// Ordering point of the LDS hand-offs inside the block sum.  A workgroup of ONE wavefront needs no barrier and no drain: the
-// DS operations of a wave execute in program order (a ds_read issued after a ds_write of another lane's slot returns the new
-// value), so the reads simply queue behind the stores and the wave stalls only where it consumes a loaded value; a
-// __syncthreads() here costs an `s_waitcnt lgkmcnt(0)` -- a full drain of the LDS queue -- three times per sum.
-#ifndef LC_WAVE_SYNC
-#define LC_WAVE_SYNC 0  // A/B switch (scripts/ubench/pnp_ab.py): 1 restores the drains for one-wave workgroups
-#endif
 // Ordering point between the lanes of ONE wavefront that hand data to each other through LDS.  The wave barrier alone is a
 // scheduling barrier (IntrNoMem); the wavefront-scope release / acquire pair around it makes the hand-off part of the memory
 // model -- the compiler may not move a lane's ds_read above another lane's ds_write across it -- and emits no instruction on
@@ -76,6 +49,61 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Sum of K doubles per lane over the 64 lanes of a ONE-wavefront workgroup, result in every lane, through LDS.
+// Lane t stores v[k] at lds[k*68 + t + 2*(t/32)] (32-double segments padded by 16 bytes, rows of 68 doubles: conflict-free
+// ds_write_b64 and ds_read_b128); lane r < 2 K sums one segment with eight + eight 16-byte reads, the two partial sums of a row meet
+// by DPP, the K totals are re-read by all lanes.  Measured cheaper than the permlane/DPP reduce-scatter + broadcast for a lone wave
+// (each 64-bit cross-lane exchange costs 25-32 cycles, scripts/ubench/fp64_latency.cpp).  Needs K <= 32 and K*68 + K doubles of LDS.
+// (Four-wave workgroups sum in registers: block_sum_waves4 below.)
+// The sum is called in two halves: block_sum_open() (the previous totals have been read), then the caller stores its K values itself
+// with block_sum_put() AS IT PRODUCES THEM -- the LDS stores of a lone wave drain at about 40 B/clk (MI355X_MICROARCH.md, LDS: one wave
+// gets half the store rate), 360 cycles for 28 doubles x 64 lanes, and issued early they drain behind the arithmetic that produces
+// the later values -- then block_sum_close() for the reduction and the broadcast.
+// The ordering points of the LDS hand-offs inside the sum are wave_sync(): a workgroup of ONE wavefront needs no barrier and no
+// drain -- the DS operations of a wave execute in program order (a ds_read issued after a ds_write of another lane's slot returns the
+// new value), so the reads simply queue behind the stores and the wave stalls only where it consumes a loaded value; a
+// __syncthreads() there costs an `s_waitcnt lgkmcnt(0)` -- a full drain of the LDS queue -- three times per sum (measured with
+// scripts/ubench/pnp_ab.py).
+constexpr int block_sum_lds_doubles(int K) { return K * 68 + K; }
+__device__ __forceinline__ int block_sum_open(int lane) {
+    wave_sync();  // the previous totals have been read
+    return lane + 2 * (lane >> 5);
+}
+__device__ __forceinline__ void block_sum_put(double* lds, int pos, int k, double v) { lds[k * 68 + pos] = v; }
+
+// sum of one 32-double segment of a row (sixteen 16-byte reads): the order every form of the LDS block sum adds a segment in
+__device__ __forceinline__ double block_sum_segment(const double2* row) {
+    double2 a[8];  // two batches of eight 16-byte reads: keeps the register peak (and so the occupancy) down
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = row[i];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const double2 t = row[8 + i];
+        a[i].x += t.x;
+        a[i].y += t.y;
+    }
+#pragma unroll
+    for (int st = 4; st >= 1; st >>= 1) {
+#pragma unroll
+        for (int i = 0; i < st; ++i) { a[i].x += a[i + st].x; a[i].y += a[i + st].y; }
+    }
+    return a[0].x + a[0].y;
+}
+
+template <int K>
+__device__ __forceinline__ void block_sum_close(double (&v)[K], double* lds, int lane) {
+    static_assert(K <= 32, "two segments per entry, one lane each");
+    wave_sync();
+    double s = 0;
+    if (lane < 2 * K) s = block_sum_segment(reinterpret_cast<const double2*>(lds + (lane / 2) * 68 + 34 * (lane % 2)));
+    s += dpp_mov_f64<kDppQuadXor1>(s, s);
+    double* tot = lds + K * 68;
+    if (lane < 2 * K && (lane % 2) == 0) tot[lane / 2] = s;
+    wave_sync();
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = tot[k];
 }
 
 // Values handed from one workgroup to another INSIDE a launch (the workgroups may sit on different XCDs, whose L2s are not
@@ -105,84 +133,10 @@ __device__ __forceinline__ void arrival_reset(unsigned* words, int tid) {
     if (tid <= kArrivalShards) xcd_store(words + tid * kArrivalStride, 0u);
 }
 
-template <int NW>
-__device__ __forceinline__ void block_sum_sync() {
-    if constexpr (NW == 1 && !LC_WAVE_SYNC) wave_sync();
-    else __syncthreads();
-}
-
-template <int NW>
-__device__ __forceinline__ int block_sum_open(int tid) {
-    block_sum_sync<NW>();  // the previous totals have been read
-    return tid + 2 * (tid >> 5);
-}
-template <int NW>
-__device__ __forceinline__ void block_sum_put(double* lds, int pos, int k, double v) { lds[k * (68 * NW) + pos] = v; }
-
-template <int K, int NW>
-__device__ __forceinline__ void block_sum_close(double (&v)[K], double* lds, int tid);
-
-template <int K, int NW>
-__device__ __forceinline__ void block_sum_bcast_lds(double (&v)[K], double* lds, int tid) {
-    const int pos = block_sum_open<NW>(tid);
-#pragma unroll
-    for (int k = 0; k < K; ++k) block_sum_put<NW>(lds, pos, k, v[k]);
-    block_sum_close<K, NW>(v, lds, tid);
-}
-
-// the reduction half alone: afterwards the K totals sit in LDS at block_sum_totals<K, NW>(lds)[0..K-1], where every thread may
-// read them until the next block_sum_open (callers that do not want all K of them in registers at once)
-template <int K, int NW>
-__device__ __forceinline__ double* block_sum_totals(double* lds) { return lds + K * (68 * NW); }
-
-// sum of one 32-double segment of a row (sixteen 16-byte reads): the order every form of the LDS block sum adds a segment in
-__device__ __forceinline__ double block_sum_segment(const double2* row) {
-    double2 a[8];  // two batches of eight 16-byte reads: keeps the register peak (and so the occupancy) down
-#pragma unroll
-    for (int i = 0; i < 8; ++i) a[i] = row[i];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const double2 t = row[8 + i];
-        a[i].x += t.x;
-        a[i].y += t.y;
-    }
-#pragma unroll
-    for (int st = 4; st >= 1; st >>= 1) {
-#pragma unroll
-        for (int i = 0; i < st; ++i) { a[i].x += a[i + st].x; a[i].y += a[i + st].y; }
-    }
-    return a[0].x + a[0].y;
-}
-
-template <int K, int NW>
-__device__ __forceinline__ void block_sum_reduce(double* lds, int tid) {
-    static_assert(K <= 32 && (NW == 1 || NW == 4), "unsupported shape");
-    constexpr int LD = 68 * NW, S = 2 * NW;
-    block_sum_sync<NW>();
-    double s = 0;
-    if (tid < K * S) s = block_sum_segment(reinterpret_cast<const double2*>(lds + (tid / S) * LD + 34 * (tid % S)));
-    s += dpp_mov_f64<kDppQuadXor1>(s, s);
-    if constexpr (NW == 4) {
-        s += dpp_mov_f64<kDppQuadXor2>(s, s);
-        s += dpp_mov_f64<kDppHalfMirror>(s, s);
-    }
-    double* tot = lds + K * LD;
-    if (tid < K * S && (tid % S) == 0) tot[tid / S] = s;
-    block_sum_sync<NW>();
-}
-
-template <int K, int NW>
-__device__ __forceinline__ void block_sum_close(double (&v)[K], double* lds, int tid) {
-    block_sum_reduce<K, NW>(lds, tid);
-    const double* tot = block_sum_totals<K, NW>(lds);
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = tot[k];
-}
-
-// The one-wave sum (NW = 1) played by a TEAM of two wavefronts that both hold all 64 values of every entry (lane = point in both:
+// The one-wave sum played by a TEAM of two wavefronts that both hold all 64 values of every entry (lane = point in both:
 // the pose unit's latency build, where half the SIMDs idle next to a wave that is bound by instruction issue).  Wave W produces and
-// stores only the entries k with k % 2 == W -- block_sum_put<1> into the slots of the one-wave form -- and sums them itself: lane
-// l < K takes segment l % 2 of entry 2 (l / 2) + W with the instruction sequence of block_sum_reduce<K, 1>, so every total has the
+// stores only the entries k with k % 2 == W -- block_sum_put into the slots of the one-wave form -- and sums them itself: lane
+// l < K takes segment l % 2 of entry 2 (l / 2) + W with the instruction sequence of block_sum_close<K>, so every total has the
 // one-wave form's bits.  A wave's rows are written and read by that wave alone (DS operations of a wave execute in program order: no
 // barrier between its stores and its reads); the K / 2 totals of each wave meet in one of TWO rows of totals behind the slots, then
 // ONE workgroup barrier, then every thread of both waves reads all K.  The rows alternate by `phase` (toggled by the call, as in
@@ -209,9 +163,7 @@ __device__ __forceinline__ void block_sum_team2(double (&v)[K], double* lds, int
 // (permlane / DPP exchanges, the data halves at every step), 16 of its lanes put its 32 wave totals into LDS, 32 threads add the four
 // rows in wave order, every thread reads the totals.  Two barriers per sum: the totals alternate between two LDS rows (`phase`,
 // toggled by the call), so a wave still reading the previous totals is never overwritten.  lds: at least 4 * 32 + 2 * 32 doubles.
-#ifndef LC_WIDE_SUM_REGS
-#define LC_WIDE_SUM_REGS 1  // A/B switch (scripts/ubench/wide_stamps.py): 0 = every thread's values through LDS
-#endif
+// (Measured with scripts/ubench/wide_stamps.py.)
 template <int K>
 __device__ __forceinline__ void block_sum_waves4(double (&v)[K], double* lds, int tid, int& phase) {
     static_assert(K <= 32, "one reduce-scatter of 32");
@@ -400,17 +352,11 @@ __device__ __forceinline__ void block_sum_parts_serial(double (&v)[K], double* l
     }
 }
 
-#ifndef LC_HORNER_ASM
-#define LC_HORNER_ASM 1  // A/B switch (scripts/ubench/pnp_ab.py)
-#endif
+// p z + c as a three-address v_fma_f64 (why: sincos_small below; measured against __builtin_fma with scripts/ubench/pnp_ab.py)
 __device__ __forceinline__ double horner_step(double p, double z, double c) {
-#if LC_HORNER_ASM
     double r;
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(p), "v"(z), "v"(c));
     return r;
-#else
-    return __builtin_fma(p, z, c);
-#endif
 }
 
 // sin and cos of a rotation angle 0 <= x <~ 8 (angle-axis norms; the LM keeps them within a few pi): Cody-Waite reduction

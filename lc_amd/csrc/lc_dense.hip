@@ -126,7 +126,7 @@ __global__ __launch_bounds__(kThreads) void lc_dense_frontend_bwd_kernel(const D
                 gx[k] = g3[0] * ns0; gy[k] = g3[1] * ns1; gz[k] = g3[2] * ns2;
             }
         }
-        constexpr bool kStream = VEC && LC_NT_GRAD_STORES;  // written once, read by the next kernel of the backward pass
+        constexpr bool kStream = VEC;  // written once, read by the next kernel of the backward pass
         if (owl) {
             map_store<V>(owl + px0, o0, kStream);
             map_store<V>(owl + HW + px0, o1, kStream);

@@ -12,15 +12,15 @@ namespace {
 
 union __attribute__((aligned(16))) DenseUnitShared {
     loss::LossSharedLoop loss;
-    double bc[pnp::kPnpLdsDoubles<4>];
+    double bc[pnp::kPnpWideReservedLdsDoubles];
 };
 
 template <int PPT>
 __global__ __launch_bounds__(256) void lc_pose_unit_dense_kernel(const LossParams lp, int T, int S, int TS, const PnpParams pp) {
     __shared__ DenseUnitShared sh;
     __shared__ unsigned ticket_sh;
-    if ((int)blockIdx.x < pp.B) pnp::solve_pose<false, 4, false, false, PPT>(pp, blockIdx.x, threadIdx.x, sh.bc);
-    else loss::tiled_workgroup<false>(lp, T, S, TS, sh.loss, ticket_sh, blockIdx.x - (unsigned)pp.B);
+    if ((int)blockIdx.x < pp.B) pnp::solve_pose<pnp::WideCached<false, PPT>>(pp, blockIdx.x, threadIdx.x, sh.bc);
+    else loss::tiled_workgroup<false>(lp, T, S, TS, sh.loss, ticket_sh);
 }
 
 }  // namespace

@@ -1,7 +1,7 @@
 // The pose-unit kernel (loss and solve workgroups in one grid), shared by lc_fused.hip (large grids) and lc_fused_latency.hip
 // (small grids: the metric's launch, compiled with the max-ILP machine scheduler, see lc_pnp_latency.hip).
 // The plain form runs one-wave workgroups: one pose or one sample each.  The TEAM form (latency build only, LC_PNP_TEAM2) runs 128-thread
-// workgroups: a solve workgroup is ONE pose solved by its two wavefronts (lc_pnp_body.h: TEAM), a loss workgroup is TWO samples, one per
+// workgroups: a solve workgroup is ONE pose solved by its two wavefronts (lc_pnp_body.h: TeamWave), a loss workgroup is TWO samples, one per
 // wavefront, each with its own LossSharedN<1> and no workgroup barrier.  At B = 256 that is 512 solve waves + 256 loss waves on the chip's
 // 1024 SIMDs, where the one-wave form leaves half of them idle for the whole launch; it is launched while every wave still gets a SIMD of
 // its own (two per pose + one per sample <= kLatencyGridMax: the kernel needs more than half a SIMD's registers).
@@ -12,14 +12,6 @@
 #pragma once
 #include "lc_loss_body.h"
 #include "lc_pnp_body.h"
-
-#ifndef LC_UNIT_PRIO
-#define LC_UNIT_PRIO 1  // A/B switch (scripts/ubench/pnp_ab.py)
-#endif
-
-#ifndef LC_UNIT_ATTR
-#define LC_UNIT_ATTR
-#endif
 
 namespace lc {
 namespace {
@@ -34,34 +26,26 @@ union __attribute__((aligned(16))) FusedSharedTeam {
 };
 
 template <int WPS, bool TEAM = false>  // WPS, see lc_pnp.hip: 1 = latency build for small grids, 2 = occupancy build for large ones
-__global__ __launch_bounds__(TEAM ? 128 : 64, WPS) LC_UNIT_ATTR void lc_pose_unit_kernel(const LossParams lp, const PnpParams pp) {
+__global__ __launch_bounds__(TEAM ? 128 : 64, WPS) void lc_pose_unit_kernel(const LossParams lp, const PnpParams pp) {
     static_assert(!TEAM || WPS == 1, "two wavefronts per pose where SIMDs idle");
     if constexpr (TEAM) {
         __shared__ FusedSharedTeam sh;
         const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
         if ((int)blockIdx.x < pp.B) {
-#if LC_UNIT_PRIO
-            __builtin_amdgcn_s_setprio(3);  // the solve is the critical path of the launch: its waves win the CU's shared issue/LDS arbitration
-#endif
-            if (wave == 0) pnp::solve_pose<true, 1, false, false, 0, false, 0, 0>(pp, blockIdx.x, lane, sh.bc, true);
-            else pnp::solve_pose<true, 1, false, false, 0, false, 0, 1>(pp, blockIdx.x, lane, sh.bc, false);
+            __builtin_amdgcn_s_setprio(3);  // the solve is the critical path of the launch: its waves win the CU's shared issue/LDS arbitration (measured: scripts/ubench/pnp_ab.py)
+            if (wave == 0) pnp::solve_pose<pnp::TeamWave<0>>(pp, blockIdx.x, lane, sh.bc, true);
+            else pnp::solve_pose<pnp::TeamWave<1>>(pp, blockIdx.x, lane, sh.bc, false);
         } else {
-#ifndef LC_UNIT_NOLOSS
             const int b = 2 * ((int)blockIdx.x - pp.B) + wave;
             if (b < lp.B) loss::sample<true, false, false, loss::LossSharedN<1>, true>(lp, b, sh.loss[wave]);
-#endif
         }
     } else {
         __shared__ FusedShared sh;
         if ((int)blockIdx.x < pp.B) {
-#if LC_UNIT_PRIO
-            __builtin_amdgcn_s_setprio(3);  // the solve is the critical path of the launch: its wave wins the CU's shared issue/LDS arbitration
-#endif
-            pnp::solve_pose<true, 1>(pp, blockIdx.x, threadIdx.x, sh.bc);
+            __builtin_amdgcn_s_setprio(3);  // the solve is the critical path of the launch: its wave wins the CU's shared issue/LDS arbitration (measured: scripts/ubench/pnp_ab.py)
+            pnp::solve_pose<pnp::OneWave<>>(pp, blockIdx.x, threadIdx.x, sh.bc);
         } else {
-#ifndef LC_UNIT_NOLOSS  // diagnostic build: what does the solve cost inside this kernel without its co-runner?
             loss::sample<true>(lp, (int)blockIdx.x - pp.B, sh.loss);
-#endif
         }
     }
 }

@@ -21,7 +21,7 @@ template <bool COV2D>
 __global__ __launch_bounds__(256) void lc_cov_loss_tiled_kernel(const LossParams p, int T, int S, int TS) {
     __shared__ loss::LossSharedLoop sh;
     __shared__ unsigned ticket_sh;
-    loss::tiled_workgroup<COV2D>(p, T, S, TS, sh, ticket_sh, blockIdx.x);
+    loss::tiled_workgroup<COV2D>(p, T, S, TS, sh, ticket_sh);
 }
 
 }  // namespace

@@ -135,9 +135,9 @@ __device__ __forceinline__ PointJac point_jac(const PoseConst& pc, const double 
 }
 
 // Workgroup-wide ordering point of the LDS hand-offs.  One-wave workgroups (N <= 64: the metric's shape) need neither a barrier nor
-// a drain of the LDS queue -- a wave's DS operations execute in program order (lc_common.h: block_sum_sync).
+// a drain of the LDS queue -- a wave's DS operations execute in program order (lc_common.h: wave_sync).
 __device__ __forceinline__ void wg_sync(int nw) {
-    if (nw == 1 && !LC_WAVE_SYNC) wave_sync();
+    if (nw == 1) wave_sync();
     else __syncthreads();
 }
 
@@ -208,29 +208,11 @@ struct GridCtx {
 // so the tickets handed out are always a prefix 0..t-1 of the grid and every sample whose T tickets are inside the prefix has all
 // its workgroups running; only the last, incomplete sample of the prefix waits for tickets not yet handed out, holds fewer than S
 // workgroup slots, and gets its siblings as soon as any earlier sample retires.
-#ifndef LC_GRID_FENCES
-#define LC_GRID_FENCES 0  // A/B switch (scripts/ubench/tiled_loss.py): 1 = plain accesses + agent-scope fences
-#endif
-__device__ __forceinline__ void grid_store(double* q, double v) {
-#if LC_GRID_FENCES
-    *q = v;
-#else
-    __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-}
-__device__ __forceinline__ double grid_load(const double* q) {
-#if LC_GRID_FENCES
-    return *q;
-#else
-    return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-}
+// (Write-through against fences, tickets against blockIdx: measured with scripts/ubench/tiled_loss.py.)
+__device__ __forceinline__ void grid_store(double* q, double v) { __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ double grid_load(const double* q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void grid_arrive_wait(GridCtx& g, int tid) {
-#if LC_GRID_FENCES
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-#else
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's write-through stores have been acknowledged
-#endif
     __syncthreads();  // ... and so have the other waves' of the workgroup
     if (tid == 0) {
         unsigned* c = g.ctr;
@@ -246,9 +228,6 @@ __device__ __forceinline__ void grid_arrive_wait(GridCtx& g, int tid) {
         }
     }
     __syncthreads();  // no wave loads a sibling's row before the poll has matched
-#if LC_GRID_FENCES
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
 }
 
 // sum over the tiles of column `col` of the sample's partial rows, in tile order
@@ -328,7 +307,7 @@ __device__ __forceinline__ auto& pick_ref(A& a, B& b) {
 template <bool REG, bool COV2D = false, bool GRID = false, typename SH = LossShared, bool WAVE = false>
 __device__ __forceinline__ void sample(const LossParams& p, const int b, SH& sh, GridCtx* gc = nullptr) {
     static_assert(!GRID || !REG, "the tiled form is a walk form");
-    static_assert(!WAVE || (REG && !LC_WAVE_SYNC), "a wave on its own has one correspondence per lane and no barrier");
+    static_assert(!WAVE || REG, "a wave on its own has one correspondence per lane and no barrier");
     constexpr bool WALK = !REG;
     const int tid = WAVE ? (int)(threadIdx.x & 63u) : (int)threadIdx.x, nthr = WAVE ? kWave : (int)blockDim.x;
     const int lane = tid & 63, wave = tid >> 6, nw = nthr >> 6;

@@ -3,28 +3,19 @@
 #pragma once
 #include "lc_loss_body.h"
 
-#ifndef LC_GRID_TICKETS
-#define LC_GRID_TICKETS 1  // A/B switch (scripts/ubench/tiled_loss.py): 0 = (sample, tile) from blockIdx (relies on in-order dispatch)
-#endif
-
 namespace lc {
 namespace loss {
 
 // Workgroups take (sample, slice) from a ticket counter as they start (see grid_arrive_wait for why that makes the hand-off
 // deadlock-free -- whatever else shares the grid: the tickets handed out are a prefix of the LOSS workgroups in start order); the
 // last workgroup of a sample to finish zeroes the sample's counters, the last sample the header, so the workspace is left as it was
-// found (all zero) for the next launch on the same stream.  block: this workgroup's index among the loss workgroups (used only
-// without tickets).
+// found (all zero) for the next launch on the same stream.
 template <bool COV2D>
-__device__ __forceinline__ void tiled_workgroup(const LossParams& p, int T, int S, int TS, LossSharedLoop& sh, unsigned& ticket_sh, unsigned block) {
+__device__ __forceinline__ void tiled_workgroup(const LossParams& p, int T, int S, int TS, LossSharedLoop& sh, unsigned& ticket_sh) {
     unsigned* head = static_cast<unsigned*>(p.workspace);
-#if LC_GRID_TICKETS
     if (threadIdx.x == 0) ticket_sh = __hip_atomic_fetch_add(head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     const unsigned ticket = ticket_sh;
-#else
-    const unsigned ticket = block;
-#endif
     const int b = (int)(ticket / (unsigned)S);
     GridCtx g;
     g.head = head;

@@ -6,28 +6,17 @@
 namespace lc {
 namespace {
 
-
-// Large grids (B > kLatencyGridMax), EXPERIMENT kept for the record (profiles/r03/occupancy.txt): the low-register form of the
-// same solve, three waves per SIMD (lc_pnp_body.h: solve_pose_lowreg).  Bit-identical, 168 VGPRs, no scratch -- and 18 % SLOWER
-// at B = 65 536 than the two-waves-per-SIMD register build (450.6 vs 381.1 us): the reads of the LDS-parked state add ~56 waits
-// on the LDS queue per iteration, which a third wave does not buy back.  Not launched unless built with -DLC_BIG_LOWREG=1.
-#ifndef LC_BIG_LOWREG
-#define LC_BIG_LOWREG 0
-#endif
-#if LC_BIG_LOWREG
-template <bool OPTS = false>
-__global__ __launch_bounds__(64, 3) void lc_pnp_lm_big_kernel(const PnpParams p) {
-    __shared__ __attribute__((aligned(16))) double bc[pnp::kPnpLowregLdsDoubles];
-    pnp::solve_pose_lowreg<OPTS>(p, blockIdx.x, threadIdx.x, bc);
-}
-#endif
+// Large grids (B > kLatencyGridMax) run lc_pnp_lm_kernel at LC_BIG_WPS waves per SIMD.  A low-register form of the solve (solve_pose_lowreg, -DLC_BIG_LOWREG=1:
+// 168 VGPRs, three waves per SIMD, the wave-uniform state parked in LDS) was bit-identical and 18 % SLOWER at B = 65 536 (450.6 vs 381.1 us,
+// profiles/r03/occupancy.txt); commit 88249e2 is the last that holds its code.
 
 // four wavefronts per pose for N > 64 (dense heads, ragged inference batches)
 // PPT: correspondences per thread kept in registers (0: block-stride loop over memory, any N); TAIL: rows may be wider than 256 PPT
 template <bool REG, bool OPTS = false, int PPT = 0, bool TAIL = false>
 __global__ __launch_bounds__(256) void lc_pnp_lm_wide_kernel(const PnpParams p) {
-    __shared__ __attribute__((aligned(16))) double bc[pnp::kPnpLdsDoubles<4>];
-    pnp::solve_pose<REG, 4, false, OPTS, PPT, TAIL>(p, blockIdx.x, threadIdx.x, bc);
+    __shared__ __attribute__((aligned(16))) double bc[pnp::kPnpWideReservedLdsDoubles];
+    if constexpr (REG) pnp::solve_pose<pnp::WideReg<OPTS>>(p, blockIdx.x, threadIdx.x, bc);
+    else pnp::solve_pose<pnp::WideCached<OPTS, PPT, TAIL>>(p, blockIdx.x, threadIdx.x, bc);
 }
 
 // Two dependent solves in one launch (lc_pnp_lm_chain_f32): workgroup w runs pose w % a.B of the first job, then pose w of the second,
@@ -36,15 +25,15 @@ __global__ __launch_bounds__(256) void lc_pnp_lm_wide_kernel(const PnpParams p) 
 // Either way the refined state reaches the second solve through 7 floats of LDS, not through a.states in global memory -- no two
 // workgroups write the same rows, nobody reads a row another workgroup is writing.
 __global__ __launch_bounds__(256) void lc_pnp_lm_chain_kernel(const PnpParams a, const PnpParams b, const int second_starts_from_first) {
-    __shared__ __attribute__((aligned(16))) double bc[pnp::kPnpLdsDoubles<4>];
+    __shared__ __attribute__((aligned(16))) double bc[pnp::kPnpWideReservedLdsDoubles];
     __shared__ float refined[8];
-    pnp::solve_pose<false, 4, false, true, 4>(a, (int)(blockIdx.x % (unsigned)a.B), threadIdx.x, bc, blockIdx.x < (unsigned)a.B, refined);
+    pnp::solve_pose<pnp::WideCached<true, 4>>(a, (int)(blockIdx.x % (unsigned)a.B), threadIdx.x, bc, blockIdx.x < (unsigned)a.B, refined);
     __syncthreads();
-    pnp::solve_pose<false, 4, false, true, 4>(b, blockIdx.x, threadIdx.x, bc, true, nullptr, second_starts_from_first ? refined : nullptr);
+    pnp::solve_pose<pnp::WideCached<true, 4>>(b, blockIdx.x, threadIdx.x, bc, true, nullptr, second_starts_from_first ? refined : nullptr);
 }
 
 // Few poses, thousands of correspondences each (the test-time solves of the dense heads: 64 objects x ~3000 selected pixels): p.split_parts
-// workgroups per pose, each with its share of the correspondences (lc_pnp_body.h: SPLIT, lc_common.h: block_sum_split).  The parts of a pose
+// workgroups per pose, each with its share of the correspondences (lc_pnp_body.h: SplitPart, lc_common.h: block_sum_split).  The parts of a pose
 // are dispatched to the same XCD (workgroups go round the 8 XCDs in launch order), so their exchange rows stay in one L2.
 template <bool OPTS>
 __global__ __launch_bounds__(256) void lc_pnp_lm_split_kernel(const PnpParams p) {
@@ -54,7 +43,7 @@ __global__ __launch_bounds__(256) void lc_pnp_lm_split_kernel(const PnpParams p)
     if (b >= p.B) return;
     SplitSum sx = split_sum_enter(static_cast<char*>(p.split_ws) + (size_t)b * kSplitPoseBytes, p.split_parts, part);
     if (threadIdx.x == 0) *reinterpret_cast<int*>(bc + 192) = 1;  // block_sum_split's "all parts arrived" (its first barrier orders this)
-    pnp::solve_pose<false, 4, false, OPTS, 8, true, 1>(p, b, threadIdx.x, bc, part == 0, nullptr, nullptr, &sx);
+    pnp::solve_pose<pnp::SplitPart<OPTS>>(p, b, threadIdx.x, bc, part == 0, nullptr, nullptr, &sx);
     if (threadIdx.x == 0) split_sum_leave(sx);
 }
 
@@ -70,17 +59,17 @@ __global__ __launch_bounds__(256) void lc_pnp_lm_split_rescue_kernel(const PnpPa
     const bool redo = __hip_atomic_load(p.rets + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == kPnpPartNeverArrived;
     if (!split_rescue_enter(region, kSplitPoseBytes, redo, (int)threadIdx.x, 256)) return;
     SplitSum sx{nullptr, nullptr, p.split_parts, 0, 0u, 0u, false};
-    pnp::solve_pose<false, 4, false, OPTS, 0, false, 2>(p, b, threadIdx.x, bc, true, nullptr, nullptr, &sx);
+    pnp::solve_pose<pnp::SplitRescue<OPTS>>(p, b, threadIdx.x, bc, true, nullptr, nullptr, &sx);
 }
 
 // diagnostic twins that also record the per-iteration trace (tests/test_gpu_pnp_trace.py)
 __global__ __launch_bounds__(64, 1) void lc_pnp_lm_trace_kernel(const PnpParams p) {
     __shared__ __attribute__((aligned(16))) double bc[pnp::kPnpLdsDoubles<1>];
-    pnp::solve_pose<true, 1, true>(p, blockIdx.x, threadIdx.x, bc);
+    pnp::solve_pose<pnp::OneWaveTrace>(p, blockIdx.x, threadIdx.x, bc);
 }
 __global__ __launch_bounds__(256) void lc_pnp_lm_wide_trace_kernel(const PnpParams p) {
-    __shared__ __attribute__((aligned(16))) double bc[pnp::kPnpLdsDoubles<4>];
-    pnp::solve_pose<false, 4, true>(p, blockIdx.x, threadIdx.x, bc);
+    __shared__ __attribute__((aligned(16))) double bc[pnp::kPnpWideReservedLdsDoubles];
+    pnp::solve_pose<pnp::WideTrace>(p, blockIdx.x, threadIdx.x, bc);
 }
 
 }  // namespace
@@ -134,56 +123,37 @@ int pnp_split_parts(int B, int Nmax) {
 }
 size_t pnp_split_workspace_bytes(int B, int Nmax) { return pnp_split_parts(B, Nmax) > 1 ? (size_t)B * kSplitPoseBytes : 0; }
 
-int launch_pnp_lm(const PnpParams& p, hipStream_t stream) {
-    if (p.B <= 0) return 0;
-    if (p.split_ws && p.split_parts > 1) {
-        const dim3 grid((unsigned)((p.B + 7) / 8 * 8 * p.split_parts));
-        if (p.options || p.weight_mask || p.pose_mod > 0) {
-            hipLaunchKernelGGL(lc_pnp_lm_split_kernel<true>, grid, dim3(256), 0, stream, p);
-            hipLaunchKernelGGL(lc_pnp_lm_split_rescue_kernel<true>, dim3((unsigned)p.B), dim3(256), 0, stream, p);
-        } else {
-            hipLaunchKernelGGL(lc_pnp_lm_split_kernel<false>, grid, dim3(256), 0, stream, p);
-            hipLaunchKernelGGL(lc_pnp_lm_split_rescue_kernel<false>, dim3((unsigned)p.B), dim3(256), 0, stream, p);
-        }
-        return hipGetLastError() == hipSuccess ? 0 : 2;
-    }
-    const bool big = p.B > kLatencyGridMax;
-    if (p.options || p.weight_mask || p.pose_mod > 0) {  // input filtering / weight forms folded into the load
-        if (p.Nmax <= 64) {
-#if LC_BIG_LOWREG
-            if (big) hipLaunchKernelGGL(lc_pnp_lm_big_kernel<true>, dim3(p.B), dim3(64), 0, stream, p);
-#else
-            if (big) hipLaunchKernelGGL((lc_pnp_lm_kernel<true, LC_BIG_WPS, true>), dim3(p.B), dim3(64), 0, stream, p);
-#endif
-            else return launch_pnp_lm_latency(p, stream);
-        } else if (p.Nmax <= 256) {
-            hipLaunchKernelGGL((lc_pnp_lm_wide_kernel<true, true>), dim3(p.B), dim3(256), 0, stream, p);
-        } else if (p.Nmax <= 1024) {
-            hipLaunchKernelGGL((lc_pnp_lm_wide_kernel<false, true, 4>), dim3(p.B), dim3(256), 0, stream, p);
-        } else if (p.Nmax <= 2048) {
-            hipLaunchKernelGGL((lc_pnp_lm_wide_kernel<false, true, 8>), dim3(p.B), dim3(256), 0, stream, p);
-        } else {  // rows wider than 2048: the first 2048 correspondences of a pose in registers, the rest (if its count gets there) from memory
-            hipLaunchKernelGGL((lc_pnp_lm_wide_kernel<false, true, 16, true>), dim3(p.B), dim3(256), 0, stream, p);
-        }
-        return hipGetLastError() == hipSuccess ? 0 : 2;
-    }
+// OPTS: the instantiations with input filtering / weight forms folded into the load.  (Two helpers, called in this order: the order in
+// which the kernels are instantiated is the order of the code object's functions.)
+template <bool OPTS>
+static int launch_pnp_lm_split(const PnpParams& p, hipStream_t stream) {
+    const dim3 grid((unsigned)((p.B + 7) / 8 * 8 * p.split_parts));
+    hipLaunchKernelGGL(lc_pnp_lm_split_kernel<OPTS>, grid, dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(lc_pnp_lm_split_rescue_kernel<OPTS>, dim3((unsigned)p.B), dim3(256), 0, stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+template <bool OPTS>
+static int launch_pnp_lm_by_width(const PnpParams& p, hipStream_t stream) {
     if (p.Nmax <= 64) {
-#if LC_BIG_LOWREG
-        if (big) hipLaunchKernelGGL(lc_pnp_lm_big_kernel<false>, dim3(p.B), dim3(64), 0, stream, p);
-#else
-        if (big) hipLaunchKernelGGL((lc_pnp_lm_kernel<true, LC_BIG_WPS>), dim3(p.B), dim3(64), 0, stream, p);
-#endif
-        else return launch_pnp_lm_latency(p, stream);
+        if (p.B <= kLatencyGridMax) return launch_pnp_lm_latency(p, stream);
+        hipLaunchKernelGGL((lc_pnp_lm_kernel<true, LC_BIG_WPS, OPTS>), dim3(p.B), dim3(64), 0, stream, p);
     } else if (p.Nmax <= 256) {
-        hipLaunchKernelGGL(lc_pnp_lm_wide_kernel<true>, dim3(p.B), dim3(256), 0, stream, p);
+        hipLaunchKernelGGL((lc_pnp_lm_wide_kernel<true, OPTS>), dim3(p.B), dim3(256), 0, stream, p);
     } else if (p.Nmax <= 1024) {
-        hipLaunchKernelGGL((lc_pnp_lm_wide_kernel<false, false, 4>), dim3(p.B), dim3(256), 0, stream, p);
+        hipLaunchKernelGGL((lc_pnp_lm_wide_kernel<false, OPTS, 4>), dim3(p.B), dim3(256), 0, stream, p);
     } else if (p.Nmax <= 2048) {
-        hipLaunchKernelGGL((lc_pnp_lm_wide_kernel<false, false, 8>), dim3(p.B), dim3(256), 0, stream, p);
-    } else {
-        hipLaunchKernelGGL((lc_pnp_lm_wide_kernel<false, false, 16, true>), dim3(p.B), dim3(256), 0, stream, p);
+        hipLaunchKernelGGL((lc_pnp_lm_wide_kernel<false, OPTS, 8>), dim3(p.B), dim3(256), 0, stream, p);
+    } else {  // rows wider than 2048: the first 2048 correspondences of a pose in registers, the rest (if its count gets there) from memory
+        hipLaunchKernelGGL((lc_pnp_lm_wide_kernel<false, OPTS, 16, true>), dim3(p.B), dim3(256), 0, stream, p);
     }
     return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+int launch_pnp_lm(const PnpParams& p, hipStream_t stream) {
+    if (p.B <= 0) return 0;
+    const bool opts = p.options || p.weight_mask || p.pose_mod > 0;
+    if (p.split_ws && p.split_parts > 1) return opts ? launch_pnp_lm_split<true>(p, stream) : launch_pnp_lm_split<false>(p, stream);
+    return opts ? launch_pnp_lm_by_width<true>(p, stream) : launch_pnp_lm_by_width<false>(p, stream);
 }
 
 }  // namespace lc

@@ -1,16 +1,18 @@
-// Device body of the batched weighted-PnP solve: one wavefront runs one pose's whole Levenberg-Marquardt solve (small grids of the plain
-// solve: a TEAM of two wavefronts that split the 28 sums of an evaluation between them, see solve_pose).
-// Included by lc_pnp.hip (stand-alone kernel) and lc_fused.hip (loss + PnP in one launch).
+// Device body of the batched weighted-PnP solve: one workgroup runs one pose's whole Levenberg-Marquardt solve -- one wavefront
+// (N <= 64), a TEAM of two wavefronts that split the 28 sums of an evaluation between them (small grids of the plain solve), or four
+// wavefronts (N > 64); see the forms in front of solve_pose.
+// Included by lc_pnp.hip / lc_pnp_latency.hip (stand-alone kernels) and lc_fused*.hip (loss + PnP in one launch).
 //
 // Replaces lib/pnp/cxx/ceres.cpp:72-145 (pnp_ceres_f32 -> ceres::Solve, DENSE_QR, autodiff Jets) and its OpenMP
 // batch driver (:147-177).  Residual model = ceres.cpp:15-65; optimiser = Ceres 2.1.0's default trust-region LM,
 // restated in oracle/pnp_lm_oracle.c (see that header for the schedule and the "parity unpinned" note).
 //
-// MI355X mapping: lane = correspondence (wave-stride when N > 64); the pose x = (angle-axis, t), the 6x6 normal
+// MI355X mapping: thread = correspondence (workgroup-stride when N > 256); the pose x = (angle-axis, t), the 6x6 normal
 // equations and the LM state are wave-uniform values every lane carries.  One evaluation per LM iteration:
 //   residuals in fp64 from R(x) X + t;  Jacobian rows from the closed form  J_rot = Jr(w) (R X x J_t)
 //   (d(R(w)X)/dw = -R [X]x Jr(w) = -[R X]x Jr(w)^T, Jr = right Jacobian of SO(3)) -- no per-point 3x3 derivative, no autodiff;
-//   J^T J (21) | J^T r (6) | r^T r (1) reduced with permlane-swap/DPP reduce-scatter + ONE LDS broadcast;
+//   J^T J (21) | J^T r (6) | r^T r (1) summed over the workgroup by the block sum of the form (lc_common.h): one wave streams its
+//   entries to LDS slots as it forms them, four waves reduce-scatter in registers and meet in 192 doubles of LDS;
 //   damped, Jacobi-scaled 6x6 system solved in registers (LDL^T, fp64).
 // Only the final 7-float state, the trust radius and the flag go back to HBM.
 // Differences from the Ceres path that do not change the iterates beyond rounding: normal equations instead of QR
@@ -46,22 +48,22 @@
 #define LC_PSTAMP(i) do {} while (0)
 #endif
 
-#ifndef LC_WIDE_REG_SUM_REGS
-#define LC_WIDE_REG_SUM_REGS 1  // A/B switch: the four-wave register block sum also on the one-correspondence-per-thread path (N <= 256: 12.4 -> 11.6 us at 64 x 256; 0 = sums streamed through LDS)
-#endif
 #ifndef LC_PNP_TEAM2
-#define LC_PNP_TEAM2 (!LC_WAVE_SYNC)  // A/B switch: the latency builds of the one-correspondence-per-lane solve (plain instantiations: lc_pnp_latency.hip, lc_fused_kernel.h) run TWO wavefronts per pose that share the products and the block sum (TEAM below); 0 = one wavefront per pose (also what the LC_WAVE_SYNC diagnostic build gets)
-#endif
-#ifndef LC_PNP_STREAM_SUM
-#define LC_PNP_STREAM_SUM 1  // A/B switch of the streamed block sum (scripts/ubench/pnp_ab.py); 1 in the shipped library
+#define LC_PNP_TEAM2 1  // A/B switch: the latency builds of the one-correspondence-per-lane solve (plain instantiations: lc_pnp_latency.hip, lc_fused_kernel.h) run TWO wavefronts per pose that share the products and the block sum (TeamWave below); 0 = one wavefront per pose
 #endif
 
 namespace lc {
 namespace pnp {
 
 template <int NW>
-constexpr int kPnpLdsDoubles = sum_bcast_lds_doubles<NW>(28);  // block_sum_bcast_lds<28, NW>
+constexpr int kPnpLdsDoubles = [] { static_assert(NW == 1, "the four-wave kernels: kPnpWideReservedLdsDoubles"); return block_sum_lds_doubles(28); }();  // block_sum_close<28>
 constexpr int kPnpTeamLdsDoubles = sum_team2_lds_doubles(28);  // block_sum_team2<28>: the one-wave slots and a second row of totals
+// Static LDS of the four-wave kernels: 7 644 doubles (61 KB) are RESERVED -- the size of a slot per thread and entry -- where
+// block_sum_waves4 touches 192 doubles (block_sum_split: 194, in the split kernels' own array).  The size is in the kernel descriptor
+// and decides how many workgroups share a compute unit, so shrinking it changes the speed and wants a measurement: kept to the byte
+// until someone takes one.
+constexpr int kPnpWideReservedLdsDoubles = 28 * 68 * 4 + 28;
+static_assert(kPnpWideReservedLdsDoubles == 7644 && kPnpWideReservedLdsDoubles >= 128 + 64, "reserved size kept; block_sum_waves4 fits");
 
 struct Point {
     double X[3];
@@ -105,7 +107,7 @@ __device__ __forceinline__ void make_rot(const double aa[3], Rot& o) {
 // FIRST: acc is written (not added to) -- saves zero-filling 32 accumulators and one add per entry when a lane owns one point.
 // STREAM: (FIRST only) every finished entry goes straight to its LDS slot of the block sum instead of into acc[]
 // PAR (STREAM only): 0 / 1 = only the entries of that parity are formed and stored (the two waves of a team, block_sum_team2); -1 = all
-template <bool FIRST, bool STREAM = false, int NW = 1, int PAR = -1>
+template <bool FIRST, bool STREAM = false, int PAR = -1>
 __device__ __forceinline__ void accumulate_point(const Point& pt, const Rot& rt, const double t[3], const double k[6],
                                                  const double (&sc)[6], double (&acc)[28], double* lds = nullptr, int pos = 0) {
     double rx[3], q[3];  // R X and R X + t
@@ -147,19 +149,19 @@ __device__ __forceinline__ void accumulate_point(const Point& pt, const Rot& rt,
         for (int j = i; j < 6; ++j) {
             if (mine(tri6(i, j))) {
                 const double v = __builtin_fma(J[0][i], J[0][j], J[1][i] * J[1][j]);
-                if constexpr (STREAM) block_sum_put<NW>(lds, pos, tri6(i, j), v);
+                if constexpr (STREAM) block_sum_put(lds, pos, tri6(i, j), v);
                 else acc[tri6(i, j)] = FIRST ? v : acc[tri6(i, j)] + v;
             }
         }
         if (mine(21 + i)) {
             const double gi = __builtin_fma(J[0][i], r[0], J[1][i] * r[1]);
-            if constexpr (STREAM) block_sum_put<NW>(lds, pos, 21 + i, gi);
+            if constexpr (STREAM) block_sum_put(lds, pos, 21 + i, gi);
             else acc[21 + i] = FIRST ? gi : acc[21 + i] + gi;
         }
     }
     if (mine(27)) {
         const double ss = __builtin_fma(r[0], r[0], r[1] * r[1]);
-        if constexpr (STREAM) block_sum_put<NW>(lds, pos, 27, ss);
+        if constexpr (STREAM) block_sum_put(lds, pos, 27, ss);
         else acc[27] = FIRST ? ss : acc[27] + ss;
     }
 }
@@ -265,36 +267,80 @@ __device__ __forceinline__ double norm6(const double (&v)[6]) {
     return fast_sqrt(m);
 }
 
-// One pose per workgroup of NW wavefronts (NW = 1: N <= 64, the metric's shape; NW = 4: larger N, e.g. the dense heads'
-// N = 1024..1849, where four waves cut the per-evaluation point loop by four; the wave-uniform LM algebra is simply
-// replicated in every wave).  bc: kPnpLdsDoubles<NW> doubles of LDS.
-// REG: Nmax <= 64*NW, each thread keeps its correspondence in registers across the whole solve.
-// TRACE: diagnostic instantiation (lc_pnp_lm_trace_f32) that also writes one row per trust-region iteration to p.trace, in the
-// column layout of oracle/pnp_lm_oracle.c's PNP_TRACE_COLS; the shipped kernels are instantiated with TRACE = false.
-// PPT (with !REG): a thread keeps its first PPT correspondences (lane, lane + 64 NW, ...) in registers as they sit in HBM (8 floats
-// each) across the whole solve; the block-stride loop otherwise re-reads them from L2 in every evaluation, ~1 us of exposed latency
-// each time.  TAIL: correspondences behind the cached prefix (n > 64 NW PPT) are read from memory; instantiations whose rows always fit
-// the prefix leave it out (the never-taken loop cost the test-time chain 1 us).  Same accumulation order, same results.
+// ---------------------------------------------------------------------------------------------------------------------
+// The forms of solve_pose.  One pose per workgroup of NW wavefronts; the wave-uniform LM algebra is replicated in every wave, the
+// forms differ in where a thread's correspondences live and in how the 28 sums of an evaluation are formed:
+//   1. ONE wave (N <= 64, the metric's shape), one correspondence per lane, in registers across the whole solve (REG).  The 28 entries
+//      are streamed to their LDS slots as they are formed, then block_sum_close<28>.  bc: kPnpLdsDoubles<1>.
+//   2. The two-wave TEAM: form 1 played by the two wavefronts of a 128-thread workgroup (TeamWave below), block_sum_team2.
+//   3. FOUR waves (N <= 256), one correspondence per thread in registers (REG): accumulate_point<true>, then block_sum_waves4.
+//   4. FOUR waves over rows of any width (e.g. the dense heads' N = 1024..1849, where four waves cut the per-evaluation point loop by
+//      four): each thread adds up its correspondences -- cached prefix, tail, rescue or plain loop, below -- then block_sum_waves4,
+//      block_sum_split, or nothing (the rescue form sums inside its loop).  bc of forms 3 and 4: kPnpWideReservedLdsDoubles.
+// A form is a struct of named constants; each one below states only what it changes from FormDefaults.
+//   OPTS: honours PnpParams::options / weight_mask / pose_mod (input filtering and weight forms of the callers, done at the load instead
+//   of by separate element-wise launches); the plain forms do not even test the fields.
+//   TRACE: diagnostic (lc_pnp_lm_trace_f32): also writes one row per trust-region iteration to p.trace, in the column layout of
+//   oracle/pnp_lm_oracle.c's PNP_TRACE_COLS.
+//   PPT (form 4): a thread keeps its first PPT correspondences (thread, thread + 256, ...) in registers as they sit in HBM (8 floats
+//   each) across the whole solve; the block-stride loop otherwise re-reads them from L2 in every evaluation, ~1 us of exposed latency
+//   each time.  TAIL: correspondences behind the cached prefix (n > 256 PPT) are read from memory; forms whose rows always fit the
+//   prefix leave it out (the never-taken loop cost the test-time chain 1 us).  Same accumulation order, same results.
+//   SPLIT = 1 (SplitPart): workgroup sx->part of the sx->G that share pose b -- it owns the correspondences part * 256 + thread + k * 256 G,
+//   the block sum runs across the G workgroups (lc_common.h: block_sum_split), everything else is replicated; part 0 stores -- status 2
+//   when its wait for another part ran out.  SPLIT = 2 (SplitRescue): ONE workgroup plays the sx->G parts in turn (the rescue launch of a
+//   pose of status 2: block_sum_parts_serial) -- per thread the same correspondences in the same order, every sum in the same order: the
+//   same bits.
+//   TEAM = 0 / 1 (TeamWave; -1 = off): wave TEAM of a 128-thread workgroup whose TWO wavefronts solve ONE pose (`lane` = lane of the
+//   wave, bc: kPnpTeamLdsDoubles).  Both waves hold all correspondences and run the whole solve -- load, quaternion -> angle-axis,
+//   make_rot, geometry and Jacobian rows, Jacobi scaling, LDL^T, the schedule: the same expressions on the same values, so they take
+//   every branch together -- but each forms, stores and sums only the 14 of the 28 entries J^T J | J^T r | r^T r of its parity
+//   (lc_common.h: block_sum_team2, one workgroup barrier per evaluation; every break / continue / return is taken by both waves, so
+//   their barrier counts agree; the n < 3 exit comes before the first).  Every total is summed in the one-wave form's order: the same
+//   bits.  Wave 0 stores (the caller passes store = false to wave 1).
+struct FormDefaults {
+    static constexpr int NW = 1, PPT = 0, SPLIT = 0, TEAM = -1;
+    static constexpr bool REG = true, OPTS = false, TRACE = false, TAIL = false;
+};
+template <bool O = false>
+struct OneWave : FormDefaults { static constexpr bool OPTS = O; };                        // form 1
+template <int W>
+struct TeamWave : FormDefaults { static constexpr int TEAM = W; };                        // form 2, wave W of the team
+struct OneWaveTrace : FormDefaults { static constexpr bool TRACE = true; };               // form 1, diagnostic
+struct FourWaves : FormDefaults { static constexpr int NW = 4; };
+template <bool O = false>
+struct WideReg : FourWaves { static constexpr bool OPTS = O; };                           // form 3
+struct WideLoop : FourWaves { static constexpr bool REG = false; };                       // form 4, every correspondence from memory
+struct WideTrace : WideLoop { static constexpr bool TRACE = true; };                      // form 4, diagnostic
+template <bool O, int P, bool T = false>
+struct WideCached : WideLoop { static constexpr bool OPTS = O, TAIL = T; static constexpr int PPT = P; };  // form 4, cached prefix
+template <bool O>
+struct SplitPart : WideCached<O, 8, true> { static constexpr int SPLIT = 1; };            // form 4, one of G workgroups of a pose
+template <bool O>
+struct SplitRescue : WideLoop { static constexpr bool OPTS = O; static constexpr int SPLIT = 2; };  // form 4, the G parts in turn
+template <class F>
+constexpr bool form_is_legal() {
+    static_assert(F::NW == 1 || F::NW == 4, "one wave or four (the team is two one-wave solves side by side)");
+    static_assert(!F::REG || (F::PPT == 0 && !F::TAIL && F::SPLIT == 0), "one correspondence per thread: nothing to cache or to walk");
+    static_assert(!F::TAIL || F::PPT > 0, "the tail is what lies behind a cached prefix");
+    static_assert(F::SPLIT != 1 || (F::NW == 4 && !F::REG && F::PPT > 0 && !F::TRACE), "the split form is the four-wave cached-prefix solve");
+    static_assert(F::SPLIT != 2 || (F::NW == 4 && !F::REG && F::PPT == 0 && !F::TRACE), "the rescue form walks memory, part by part");
+    static_assert(F::TEAM < 0 || (F::TEAM <= 1 && F::REG && F::NW == 1 && !F::TRACE && !F::OPTS && F::SPLIT == 0), "the team form is the plain one-correspondence-per-lane solve");
+    return true;
+}
+
 // store / handoff / start_override (the chained launch, lc_pnp.hip): store = false keeps the job's outputs in registers (a workgroup that
 // repeats a solve another workgroup owns must not write the owner's rows a second time); handoff (7 floats of LDS) receives the state the
 // solve would leave in p.states[b]; start_override replaces the start pose (7 floats, e.g. a previous solve's handoff).
-// SPLIT = 1 (NW = 4, PPT > 0): workgroup sx->part of the sx->G that share pose b -- it owns the correspondences part * 64 NW + lane + k * 64 NW G,
-// the block sum runs across the G workgroups (lc_common.h: block_sum_split), everything else is replicated; part 0 stores -- status 2 when
-// its wait for another part ran out.  SPLIT = 2 (NW = 4, PPT = 0): ONE workgroup plays the sx->G parts in turn (the rescue launch of a pose
-// of status 2: block_sum_parts_serial) -- per thread the same correspondences in the same order, every sum in the same order: the same bits.
-// TEAM = 0 / 1 (REG, NW = 1; -1 = off): wave TEAM of a 128-thread workgroup whose TWO wavefronts solve ONE pose (`lane` = lane of the wave, bc:
-// kPnpTeamLdsDoubles).  Both waves hold all correspondences and run the whole solve -- load, quaternion -> angle-axis, make_rot, geometry and
-// Jacobian rows, Jacobi scaling, LDL^T, the schedule: the same expressions on the same values, so they take every branch together -- but each
-// forms, stores and sums only the 14 of the 28 entries J^T J | J^T r | r^T r of its parity (lc_common.h: block_sum_team2, one workgroup
-// barrier per evaluation; every break / continue / return is taken by both waves, so their barrier counts agree; the n < 3 exit comes before
-// the first).  Every total is summed in the one-wave form's order: the same bits.  Wave 0 stores (the caller passes store = false to wave 1).
-template <bool REG, int NW = 1, bool TRACE = false, bool OPTS = false, int PPT = 0, bool TAIL = false, int SPLIT = 0, int TEAM = -1>
+// `lane`: the thread index within the workgroup (TeamWave: within the wave); sx: SplitPart / SplitRescue only.
+template <class F>
 __device__ __forceinline__ void solve_pose(const PnpParams& p, int b, int lane, double* bc, bool store = true, float* handoff = nullptr,
                                            const float* start_override = nullptr, [[maybe_unused]] SplitSum* sx = nullptr) {
-    constexpr int kThreads = kWave * NW;  // `lane` is the thread index within the workgroup
-    static_assert(SPLIT != 1 || (NW == 4 && !REG && PPT > 0 && !TRACE), "the split form is the four-wave cached-prefix solve");
-    static_assert(SPLIT != 2 || (NW == 4 && !REG && PPT == 0 && !TRACE), "the rescue form walks memory, part by part");
-    static_assert(TEAM < 0 || (TEAM <= 1 && REG && NW == 1 && !TRACE && SPLIT == 0), "the team form is the one-correspondence-per-lane solve");
+    constexpr int NW = F::NW, PPT = F::PPT, SPLIT = F::SPLIT, TEAM = F::TEAM;
+    constexpr bool REG = F::REG, OPTS = F::OPTS, TRACE = F::TRACE, TAIL = F::TAIL;
+    static_assert(form_is_legal<F>());
+    static_assert(NW == 4 || REG, "one wave has one correspondence per lane");
+    constexpr int kThreads = kWave * NW;
     const int slot = SPLIT == 1 ? lane + kThreads * sx->part : lane;  // first correspondence of this thread, and the distance to its next
     const int stride = SPLIT == 1 ? kThreads * sx->G : kThreads;
 #ifdef LC_TRACE_CLOCK
@@ -373,7 +419,7 @@ __device__ __forceinline__ void solve_pose(const PnpParams& p, int b, int lane, 
         if (!active) { rp.a = 0.0; rp.b = 0.0; rp.c = 0.0; }
     }
 
-    [[maybe_unused]] int sum_phase = 0;  // block_sum_waves4 / block_sum_team2: which of its two rows of totals the next sum writes
+    [[maybe_unused]] int sum_phase = 0;  // block_sum_waves4 / block_sum_split / block_sum_team2: which of its two rows of totals the next sum writes
     // full evaluation at xe with column scaling sc: H = Js^T Js (21), g = Js^T r (6), cost; false when anything is non-finite
     auto evaluate = [&](const double (&xe)[6], const double (&sc)[6], double (&H)[21], double (&g)[6], double& cost) -> bool {
         LC_PSTAMP(1);
@@ -382,31 +428,32 @@ __device__ __forceinline__ void solve_pose(const PnpParams& p, int b, int lane, 
         LC_PSTAMP(2);
         const double t[3] = {xe[3], xe[4], xe[5]};
         double acc[28];
-        if constexpr (TEAM >= 0) {
-            // this wave's half of the 28 partial sums goes to LDS as it is produced; the sibling wave forms the other half
-            const int pos = block_sum_open<1>(lane);
-            accumulate_point<true, true, 1, TEAM>(rp, rt, t, cam, sc, acc, bc, pos);
+        if constexpr (NW == 1 && TEAM < 0) {
+            // form 1.  Lanes beyond n hold zero-weight copies (exact zeros); the 28 partial sums go to LDS as they are produced
+            const int pos = block_sum_open(lane);
+            accumulate_point<true, true>(rp, rt, t, cam, sc, acc, bc, pos);
+            LC_PSTAMP(3);
+            block_sum_close<28>(acc, bc, lane);
+        } else if constexpr (NW == 1) {
+            // form 2.  This wave's half of the 28 partial sums goes to LDS as it is produced; the sibling wave forms the other half
+            const int pos = block_sum_open(lane);
+            accumulate_point<true, true, TEAM>(rp, rt, t, cam, sc, acc, bc, pos);
             LC_PSTAMP(3);
             block_sum_team2<28, TEAM>(acc, bc, lane, sum_phase);
-        } else if constexpr (REG && LC_PNP_STREAM_SUM && !(NW == 4 && LC_WIDE_REG_SUM_REGS)) {
-            // lanes beyond n hold zero-weight copies (exact zeros); the 28 partial sums go to LDS as they are produced
-            const int pos = block_sum_open<NW>(lane);
-            accumulate_point<true, true, NW>(rp, rt, t, cam, sc, acc, bc, pos);
-            LC_PSTAMP(3);
-            block_sum_close<28, NW>(acc, bc, lane);
         } else if constexpr (REG) {
+            // form 3.  The register block sum here too: 12.4 -> 11.6 us at 64 x 256 against sums streamed through LDS
             accumulate_point<true>(rp, rt, t, cam, sc, acc);
             LC_PSTAMP(3);
-            if constexpr (NW == 4 && LC_WIDE_SUM_REGS) block_sum_waves4<28>(acc, bc, lane, sum_phase);
-            else block_sum_bcast_lds<28, NW>(acc, bc, lane);
+            block_sum_waves4<28>(acc, bc, lane, sum_phase);
         } else {
+            // form 4
 #pragma unroll
             for (int i = 0; i < 28; ++i) acc[i] = 0;
             if constexpr (PPT > 0) {
 #pragma unroll
                 for (int k = 0; k < PPT; ++k)
                     if (slot + k * stride < n) accumulate_point<false>(to_point(rawc[k], cam), rt, t, cam, sc, acc);
-                // rows wider than the cached prefix (Nmax > 64 NW PPT): the correspondences behind it from memory, in the same per-thread
+                // rows wider than the cached prefix (Nmax > 256 PPT): the correspondences behind it from memory, in the same per-thread
                 // order as the plain loop below -- same sums bit for bit; empty when the pose's count fits the prefix
                 if constexpr (TAIL)
                     for (int i = slot + PPT * stride; i < n; i += stride) accumulate_point<false>(load_point<OPTS>(p, base, i, cam), rt, t, cam, sc, acc);
@@ -425,8 +472,7 @@ __device__ __forceinline__ void solve_pose(const PnpParams& p, int b, int lane, 
             LC_PSTAMP(3);
             if constexpr (SPLIT == 2) {}
             else if constexpr (SPLIT == 1) block_sum_split<28>(acc, bc, lane, sum_phase, *sx);
-            else if constexpr (NW == 4 && LC_WIDE_SUM_REGS) block_sum_waves4<28>(acc, bc, lane, sum_phase);
-            else block_sum_bcast_lds<28, NW>(acc, bc, lane);
+            else block_sum_waves4<28>(acc, bc, lane, sum_phase);
         }
         LC_PSTAMP(4);
 #pragma unroll
@@ -614,269 +660,6 @@ __device__ __forceinline__ void solve_pose(const PnpParams& p, int b, int lane, 
                 if (store) p.states[7 * (size_t)b + k] = stq[k];
                 if (handoff) handoff[k] = stq[k];
             }
-        }
-    }
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The same solve for LARGE grids (B > kLatencyGridMax poses: several waves per SIMD, throughput matters, not one wave's latency)
-// in at most 168 VGPRs, so that THREE waves fit a SIMD instead of two.  solve_pose keeps every wave-uniform quantity of the solve
-// -- the 21 + 6 entries of the normal equations, pose, candidate, Jacobi scaling and its inverse: ~60 doubles = 120 VGPRs that
-// hold the same value in all 64 lanes -- in registers; here they live in LDS (the block sum's 28 totals stay where the reduction
-// leaves them, x / scale / 1/scale in a 24-double block behind them) and are read (ds_read_b64 of one address: a broadcast) where
-// an expression needs them.  With three waves per SIMD the extra LDS latency is covered by the other waves.
-// The arithmetic is solve_pose<true, 1>'s, expression for expression: same results bit for bit
-// (tests/test_gpu_pnp.py::test_large_grid_build_equals_the_latency_build).
-constexpr int kPnpLowregLdsDoubles = kPnpLdsDoubles<1> + 30;
-
-// (A + diag(dg)) y = g with A (packed upper 21), g and the LM diagonal read from LDS; returns ok, y and the model cost change
-__device__ __forceinline__ bool ldlt_solve6_lds(const double* A, const double* g, double inv_radius, double (&y)[6], double& mcc) {
-    double L[6][6], Ld[6][6], id[6];
-    bool ok = true;
-    auto dgv = [&](int i) { return fmin(fmax(A[tri6(i, i)], 1e-6), 1e32) * inv_radius; };
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double dj = A[tri6(j, j)] + dgv(j);
-#pragma unroll
-        for (int k = 0; k < j; ++k) dj -= L[j][k] * Ld[j][k];
-        ok = ok && (dj > 0) && (dj < DBL_MAX);
-        id[j] = fast_rcp(dj);
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = A[tri6(j, i)];
-#pragma unroll
-            for (int k = 0; k < j; ++k) v -= L[i][k] * Ld[j][k];
-            Ld[i][j] = v;
-            L[i][j] = v * id[j];
-        }
-    }
-    double z[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double v = g[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) v -= L[i][k] * z[k];
-        z[i] = v;
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = z[i] * id[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) v -= L[k][i] * y[k];
-        y[i] = v;
-    }
-    mcc = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) mcc += y[i] * (g[i] + dgv(i) * y[i]);
-    mcc *= 0.5;
-    return ok;
-}
-
-template <bool OPTS = false>
-__device__ __forceinline__ void solve_pose_lowreg(const PnpParams& p, int b, int lane, double* bc) {
-    const int n = p.counts ? p.counts[b] : p.Nmax;
-    const int bk = (OPTS && p.pose_mod > 0) ? b % p.pose_mod : b;
-    const float* st_in = (p.start ? p.start + 7 * (size_t)bk : p.states + 7 * (size_t)b);
-    const bool filter = OPTS && (p.options & kPnpNanToNum);
-    auto fin = [&](float f) { return filter ? nan_to_num(f) : f; };
-    if (n < 3) {  // ceres.cpp:84-91
-        if (lane == 0) {
-            p.rets[b] = 1;
-            p.result_tr[b] = 1.f;
-            if (p.iters) p.iters[b] = 0;
-        }
-        if ((p.start || filter) && lane < 7) p.states[7 * (size_t)b + lane] = fin(st_in[lane]);
-        return;
-    }
-    const size_t base = (size_t)b * p.Nmax;
-    const bool active = lane < n;
-    const RawPoint raw = load_raw_point<OPTS>(p, base, active ? lane : 0);
-    double cam[6];
-    {
-        const float* Kp = p.K + 9 * (size_t)bk;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) cam[i] = fin(Kp[i]);
-    }
-    // LDS: tot[0..20] = H, tot[21..26] = g, tot[27] = r.r of the last evaluation; us: x | scale | iscale | candidate
-    double* const tot = block_sum_totals<28, 1>(bc);
-    double* const ux = bc + kPnpLdsDoubles<1>;
-    double* const uscale = ux + 6;
-    double* const uiscale = ux + 12;
-    double* const uxc = ux + 18;
-    double* const ucam = ux + 24;  // K[0,0], K[0,1], -, K[1,0], K[1,1], - (the principal point is folded into the measurements)
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) ucam[i] = cam[i];
-    }
-    {
-        double x[6];
-        const double q0 = fin(st_in[0]), q1 = fin(st_in[1]), q2 = fin(st_in[2]), q3 = fin(st_in[3]);
-        const double s2 = q1 * q1 + q2 * q2 + q3 * q3;
-        double kk = 2.0;
-        if (s2 > 0.0) {
-            const double s = fast_sqrt(s2);
-            const double half = atan_ratio_pos(s, fabs(q0));
-            const double two_theta = 2.0 * ((q0 < 0.0) ? -half : half);
-            kk = two_theta / s;
-        }
-        x[0] = q1 * kk; x[1] = q2 * kk; x[2] = q3 * kk;
-        x[3] = fin(st_in[4]); x[4] = fin(st_in[5]); x[5] = fin(st_in[6]);
-        if (lane == 0) {
-#pragma unroll
-            for (int j = 0; j < 6; ++j) { ux[j] = x[j]; uscale[j] = 1.0; }
-        }
-        wave_sync();
-    }
-    Point rp = to_point(raw, cam);
-    if (!active) { rp.a = 0.0; rp.b = 0.0; rp.c = 0.0; }
-
-    // evaluation at xe (6 doubles in LDS) with the column scaling in uscale: the 28 totals stay in LDS; returns the cost, false when non-finite
-    auto evaluate = [&](const double* xe, double& cost) -> bool {
-        double xv[6], sc[6];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) { xv[j] = xe[j]; sc[j] = uscale[j]; }
-        Rot rt;
-        make_rot(xv, rt);
-        const double t[3] = {xv[3], xv[4], xv[5]};
-        double acc[28];
-        const int pos = block_sum_open<1>(lane);
-        accumulate_point<true, true, 1>(rp, rt, t, ucam, sc, acc, bc, pos);
-        block_sum_reduce<28, 1>(bc, lane);
-        const double ss = tot[27];
-        cost = 0.5 * ss;
-        double chk = ss;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) chk += tot[tri6(i, i)];
-        return chk <= DBL_MAX;
-    };
-
-    const double ftol = p.ftol, ptol = 1e-8, gtol = 1e-10;
-    double cost;
-    bool failed = !evaluate(ux, cost);
-    {   // Jacobi scaling 1/(1+||J_j||), fixed at iteration 0; the totals become those of the scaled problem
-        double scale[6], iscale[6];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            iscale[j] = 1.0 + fast_sqrt(tot[tri6(j, j)]);
-            scale[j] = fast_rcp(iscale[j]);
-        }
-        double Hs[21], gs[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-#pragma unroll
-            for (int j = i; j < 6; ++j) { double h = tot[tri6(i, j)]; h *= scale[i] * scale[j]; Hs[tri6(i, j)] = h; }
-            double gi = tot[21 + i]; gi *= scale[i]; gs[i] = gi;
-        }
-        wave_sync();  // every lane has read the unscaled totals
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < 21; ++k) tot[k] = Hs[k];
-#pragma unroll
-            for (int j = 0; j < 6; ++j) { tot[21 + j] = gs[j]; uscale[j] = scale[j]; uiscale[j] = iscale[j]; }
-        }
-        wave_sync();
-    }
-    auto grad_max = [&]() {  // max-norm of the UNSCALED gradient J^T r
-        double m = 0;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) m = fmax(m, fabs(tot[21 + j]) * uiscale[j]);
-        return m;
-    };
-    auto sqnorm6 = [](const double* v) {
-        double m = 0;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) m += v[j] * v[j];
-        return m;
-    };
-    double gmax = grad_max();
-    double xn2 = sqnorm6(ux);
-    double radius = 1e4, dfac = 2.0;
-    int iter = 0, n_invalid = 0;
-    bool converged = false;
-
-    while (uniform(!failed && !converged)) {
-        if (iter >= p.max_iter) break;
-        if (uniform(gmax <= gtol || radius <= 1e-32)) { converged = true; break; }
-        ++iter;
-        double y[6], mcc;
-        const double inv_radius = fast_rcp(radius);
-        bool step_ok = ldlt_solve6_lds(tot, tot + 21, inv_radius, y, mcc);
-        step_ok = step_ok && (mcc > 0.0) && (mcc <= DBL_MAX);
-        if (uniform(!step_ok)) {  // HandleInvalidStep
-            if (++n_invalid >= 5) { failed = true; break; }
-            radius /= dfac; dfac *= 2.0;
-            continue;
-        }
-        n_invalid = 0;
-        double sn2;
-        {
-            double xc[6], delta[6];
-#pragma unroll
-            for (int j = 0; j < 6; ++j) { delta[j] = -y[j] * uscale[j]; xc[j] = ux[j] + delta[j]; }
-            sn2 = 0;
-#pragma unroll
-            for (int j = 0; j < 6; ++j) sn2 += delta[j] * delta[j];
-            if (lane == 0) {
-#pragma unroll
-                for (int j = 0; j < 6; ++j) uxc[j] = xc[j];
-            }
-            wave_sync();
-        }
-        const bool ptol_in_reach = uniform(!(sn2 > 2.0 * ptol * ptol * (xn2 + ptol * ptol)));
-        bool ptol_hit = false;
-        if (ptol_in_reach) ptol_hit = uniform(fast_sqrt(sn2) <= ptol * (fast_sqrt(xn2) + ptol));
-        double cost_c;
-        const bool cand_ok = evaluate(uxc, cost_c);
-        if (!cand_ok) cost_c = DBL_MAX;
-        if (ptol_hit) { converged = true; break; }  // ParameterToleranceReached
-        const double cost_change = cost - cost_c;
-        if (uniform(fabs(cost_change) <= ftol * cost)) { converged = true; break; }  // FunctionToleranceReached
-        const double rel = cost_change * fast_rcp(mcc);
-        if (uniform(rel > 1e-3)) {  // HandleSuccessfulStep
-            double xn[6];
-#pragma unroll
-            for (int j = 0; j < 6; ++j) xn[j] = uxc[j];
-            wave_sync();
-            if (lane == 0) {
-#pragma unroll
-                for (int j = 0; j < 6; ++j) ux[j] = xn[j];
-            }
-            wave_sync();
-            cost = cost_c;
-            xn2 = sqnorm6(ux);
-            gmax = grad_max();
-            const double tq = 2.0 * rel - 1.0;
-            radius = fmin(1e16, radius * fast_rcp(fmax(1.0 / 3.0, 1.0 - tq * tq * tq)));
-            dfac = 2.0;
-        } else {
-            radius /= dfac; dfac *= 2.0;
-            double cost_again;
-            if (!evaluate(ux, cost_again)) { failed = true; break; }
-        }
-    }
-    const bool invalid = failed || !converged;
-    if (invalid && (p.start || filter) && lane < 7) p.states[7 * (size_t)b + lane] = fin(st_in[lane]);
-    if (lane == 0) {
-        p.rets[b] = invalid ? 1 : 0;
-        p.result_tr[b] = (float)radius;
-        if (p.iters) p.iters[b] = iter;
-        if (!invalid) {  // ceres.cpp:131-144: AngleAxisToQuaternion, write back in place
-            float* st = p.states + 7 * (size_t)b;
-            double x[6];
-#pragma unroll
-            for (int j = 0; j < 6; ++j) x[j] = ux[j];
-            const double t2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
-            double q0 = 1.0, kk = 0.5;
-            if (t2 > 0.0) {
-                const double th = fast_sqrt(t2), h = 0.5 * th;
-                double sh, ch;
-                sincos_small(h, sh, ch);
-                q0 = ch;
-                kk = sh / th;
-            }
-            st[0] = (float)q0; st[1] = (float)(x[0] * kk); st[2] = (float)(x[1] * kk); st[3] = (float)(x[2] * kk);
-            st[4] = (float)x[3]; st[5] = (float)x[4]; st[6] = (float)x[5];
         }
     }
 }

@@ -9,18 +9,21 @@ namespace {
 // idle anyway, spilling would only lengthen the lone wave), 2 for large grids (+43 % throughput at B = 16384).
 // OPTS: honours PnpParams::options / weight_mask (lc_pnp_lm2_f32); the plain instantiations are the ones the metric runs
 // TEAM (latency build of the plain solve, LC_PNP_TEAM2): 128-thread workgroups, TWO wavefronts per pose, each with half of the products and of
-// the block sum (lc_pnp_body.h: TEAM); the same bits as the one-wave forms
+// the block sum (lc_pnp_body.h: TeamWave); the same bits as the one-wave forms
+// REG is always true (one wave has one correspondence per lane).  It stays in the parameter list because the list is part of the kernel's
+// mangled name, which tests/launch_forms.py and scripts/kernel_resources.py match.
 template <bool REG, int WPS, bool OPTS = false, bool TEAM = false>
 __global__ __launch_bounds__(TEAM ? 128 : 64, WPS) void lc_pnp_lm_kernel(const PnpParams p) {
+    static_assert(REG, "one wave: one correspondence per lane");
     if constexpr (TEAM) {
-        static_assert(REG && WPS == 1 && !OPTS, "two wavefronts per pose where SIMDs idle");
+        static_assert(WPS == 1 && !OPTS, "two wavefronts per pose where SIMDs idle");
         __shared__ __attribute__((aligned(16))) double bc[pnp::kPnpTeamLdsDoubles];
         const int lane = threadIdx.x & 63;
-        if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0) pnp::solve_pose<true, 1, false, false, 0, false, 0, 0>(p, blockIdx.x, lane, bc, true);
-        else pnp::solve_pose<true, 1, false, false, 0, false, 0, 1>(p, blockIdx.x, lane, bc, false);
+        if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0) pnp::solve_pose<pnp::TeamWave<0>>(p, blockIdx.x, lane, bc, true);
+        else pnp::solve_pose<pnp::TeamWave<1>>(p, blockIdx.x, lane, bc, false);
     } else {
         __shared__ __attribute__((aligned(16))) double bc[pnp::kPnpLdsDoubles<1>];
-        pnp::solve_pose<REG, 1, false, OPTS>(p, blockIdx.x, threadIdx.x, bc);
+        pnp::solve_pose<pnp::OneWave<OPTS>>(p, blockIdx.x, threadIdx.x, bc);
     }
 }
 

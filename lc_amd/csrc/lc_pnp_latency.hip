@@ -19,9 +19,9 @@ namespace {
 __global__ __launch_bounds__(64, 1) void lc_pnp_lm_chain_small_kernel(const PnpParams a, const PnpParams b, const int second_starts_from_first) {
     __shared__ __attribute__((aligned(16))) double bc[pnp::kPnpLdsDoubles<1>];
     __shared__ float refined[8];
-    pnp::solve_pose<true, 1, false, true>(a, (int)(blockIdx.x % (unsigned)a.B), threadIdx.x, bc, blockIdx.x < (unsigned)a.B, refined);
+    pnp::solve_pose<pnp::OneWave<true>>(a, (int)(blockIdx.x % (unsigned)a.B), threadIdx.x, bc, blockIdx.x < (unsigned)a.B, refined);
     __syncthreads();
-    pnp::solve_pose<true, 1, false, true>(b, blockIdx.x, threadIdx.x, bc, true, nullptr, second_starts_from_first ? refined : nullptr);
+    pnp::solve_pose<pnp::OneWave<true>>(b, blockIdx.x, threadIdx.x, bc, true, nullptr, second_starts_from_first ? refined : nullptr);
 }
 }  // namespace
 

@@ -449,3 +449,20 @@ def test_shared_loader_refuses_what_it_cannot_rebuild(name, tmp_path, monkeypatc
         assert msg.endswith("set LC_AMD_ALLOW_STALE=1 to load it as it is")
     others = {build.source_hash(t) for t in build.all_targets() if t.name != name}
     assert not any(h in msg for h in others)
+
+
+def test_every_build_switch_is_listed_in_the_design():
+    """The names the kernels' sources test with #ifdef / #ifndef (the per-library source-hash macros apart) are exactly the rows of
+    DESIGN.md's table of build switches: a new switch cannot appear without an entry that says who sets it, and a folded one leaves
+    the table with its code."""
+    import glob
+
+    in_sources = set()
+    for path in glob.glob(os.path.join(ROOT, "lc_amd", "csrc", "**", "*"), recursive=True):
+        if os.path.isfile(path):
+            in_sources |= set(re.findall(r"^\s*#\s*ifn?def\s+(LC_\w+)", open(path).read(), re.M))
+    in_sources = {n for n in in_sources if not re.fullmatch(r"LC_AMD_\w*SRC_HASH", n)}
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    table = design[design.index("## 9. Build switches"):]
+    listed = set(re.findall(r"^\| `(LC_\w+)` \|", table, re.M))
+    assert len(in_sources) >= 10 and in_sources == listed, (sorted(in_sources - listed), sorted(listed - in_sources))
