@@ -31,6 +31,38 @@ def _quat_to_R(q):
     return o.reshape(q.shape[:-1] + (3, 3))
 
 
+# ---- crop cameras.  The reference hands every K-reading function `out_K = affine33 @ cam_K` (dataset.py:421-423): a BOP camera with
+# fx != fy and cx != cy behind the crop's scaled in-plane rotation, so K[:2,:2] = s Rot diag(fx, fy).  "rot" (the default, and the only form
+# before the keyword existed) is the scaled rotation alone with the principal point at the centre; the other two are formed from the same
+# f and theta without a random draw, so every other tensor of a (shape, seed) keeps its bits ----
+CAMERAS = {
+    "rot": None,
+    "bop": ((1.0, 0.0), (0.0, 573.57043 / 572.4114)),   # LM-O's fy / fx
+    "stress": ((1.15, 0.08), (0.0, 0.87)),              # anisotropy and skew large enough that a swapped or transposed entry shows in any output
+}
+PRINCIPAL_SHIFT = (9.25, -14.5)  # px, both non-default cameras: cx != cy
+
+
+def crop_camera(f, th, cx, cy, camera="rot"):
+    """(B,3,3) float64: K[:2,:2] = f Rot(th) M with M = I ("rot"), diag(1, fy/fx) ("bop") or an upper-triangular stretch + skew ("stress");
+    principal point (cx, cy), shifted by PRINCIPAL_SHIFT for the latter two."""
+    if camera not in CAMERAS:
+        raise ValueError(f"camera must be one of {sorted(CAMERAS)}, not {camera!r}")
+    K = torch.zeros(f.shape[0], 3, 3, dtype=torch.float64)
+    K[:, 0, 0] = f * th.cos()
+    K[:, 0, 1] = -f * th.sin()
+    K[:, 1, 0] = f * th.sin()
+    K[:, 1, 1] = f * th.cos()
+    K[:, 0, 2] = cx
+    K[:, 1, 2] = cy
+    K[:, 2, 2] = 1
+    if CAMERAS[camera] is not None:
+        K[:, :2, :2] = K[:, :2, :2] @ torch.tensor(CAMERAS[camera], dtype=torch.float64)
+        K[:, 0, 2] += PRINCIPAL_SHIFT[0]
+        K[:, 1, 2] += PRINCIPAL_SHIFT[1]
+    return K
+
+
 def bbox3d_from_scale(scale: torch.Tensor) -> torch.Tensor:
     """8 corners in the order of `model_transform.py:6-18`."""
     signs = torch.tensor([[1, 1, 1], [1, 1, -1], [1, -1, 1], [1, -1, -1],
@@ -39,8 +71,9 @@ def bbox3d_from_scale(scale: torch.Tensor) -> torch.Tensor:
 
 
 def make_batch(B: int, N: int, seed: int = 0, dtype=torch.float32, outlier_frac: float = 0.05,
-               rotate_K: bool = True, noise_px: float = 1.0):
-    """Returns a dict of CPU tensors: K, pose, pts3d, pts2d, inv_std, bbox_3d, start (perturbed pose for PnP)."""
+               rotate_K: bool = True, noise_px: float = 1.0, camera: str = "rot"):
+    """Returns a dict of CPU tensors: K, pose, pts3d, pts2d, inv_std, bbox_3d, start (perturbed pose for PnP).  `camera`: CAMERAS; the
+    points are projected with the K it names, so the correspondences stay consistent with `pose`."""
     g = torch.Generator().manual_seed(seed)
     f64 = torch.float64
     q = torch.randn(B, 4, generator=g, dtype=f64)
@@ -53,14 +86,7 @@ def make_batch(B: int, N: int, seed: int = 0, dtype=torch.float32, outlier_frac:
     X = (torch.rand(B, N, 3, generator=g, dtype=f64) * 2 - 1) * ext
     f = torch.rand(B, generator=g, dtype=f64) * 100 + 200
     th = torch.rand(B, generator=g, dtype=f64) * (2 * math.pi) if rotate_K else torch.zeros(B, dtype=f64)
-    K = torch.zeros(B, 3, 3, dtype=f64)
-    K[:, 0, 0] = f * th.cos()
-    K[:, 0, 1] = -f * th.sin()
-    K[:, 1, 0] = f * th.sin()
-    K[:, 1, 1] = f * th.cos()
-    K[:, 0, 2] = 32
-    K[:, 1, 2] = 32
-    K[:, 2, 2] = 1
+    K = crop_camera(f, th, 32, 32, camera)
     R = _quat_to_R(q)
     Xc = X @ R.mT + t[:, None]
     xf = Xc @ K.mT
@@ -177,7 +203,7 @@ TEST_TIME_CONFIGS = {
 }
 
 
-def test_time_inputs(name: str, B: int = 64, seed: int = 0, flip: float = 0.02, train: bool = False):
+def test_time_inputs(name: str, B: int = 64, seed: int = 0, flip: float = 0.02, train: bool = False, camera: str = "rot"):
     """Synthetic network outputs of the dense heads at test time, shaped like the named config's: every object is an ellipsoid with the
     LM-O extents seen under a random pose, rendered by ray casting (so pixel <-> model point correspondences are exact up to the noise
     added below and the visible region is a blob of ~20-30 % of the crop); zlmo: 21 code planes (Gray code of the
@@ -186,7 +212,8 @@ def test_time_inputs(name: str, B: int = 64, seed: int = 0, flip: float = 0.02, 
     -> (cfg dict for AttrDict, gt_dict, out_dict) of CPU tensors; gt_dict['pose_best'] is the pose to recover.
     `train=True` adds what `Loss_fn.forward` reads at training time (`losses.py:49-67,132-139`: `msk_noc`, `xyz_noc_tgt` or the code
     targets `xyz_noc_bin_tgt / _raw`), an occluder over part of `msk_vis`, and gross errors on a few pixels of the xyz head; every extra
-    random draw comes after the test-time ones, so the test-time tensors of a (name, B, seed) do not depend on the flag."""
+    random draw comes after the test-time ones, so the test-time tensors of a (name, B, seed) do not depend on the flag.
+    `camera`: CAMERAS; the rays are cast through the K it names (the object's translation is still placed with the drawn f)."""
     from . import floatbits as fb
 
     spec = TEST_TIME_CONFIGS[name]
@@ -200,9 +227,7 @@ def test_time_inputs(name: str, B: int = 64, seed: int = 0, flip: float = 0.02, 
     ext = torch.tensor(EXTENT_MM, dtype=f64)
     f = (torch.rand(B, generator=g, dtype=f64) * 0.15 + 0.55) * W * z / (2 * ext.max())  # the object spans 55-70 % of the crop's width (zoomed crops, dataset.py:402-423)
     th = torch.rand(B, generator=g, dtype=f64) * (2 * math.pi)
-    K = torch.zeros(B, 3, 3, dtype=f64)
-    K[:, 0, 0], K[:, 0, 1], K[:, 1, 0], K[:, 1, 1] = f * th.cos(), -f * th.sin(), f * th.sin(), f * th.cos()
-    K[:, 0, 2], K[:, 1, 2], K[:, 2, 2] = W / 2, H / 2, 1
+    K = crop_camera(f, th, W / 2, H / 2, camera)
     t = torch.stack(((torch.rand(B, generator=g, dtype=f64) - 0.5) * 0.15 * W * z / f, (torch.rand(B, generator=g, dtype=f64) - 0.5) * 0.15 * H * z / f, z), -1)
     R = _quat_to_R(q)
     # ray casting in the model frame: o + s d on the ellipsoid |x / ext| = 1, nearest hit

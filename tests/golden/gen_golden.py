@@ -114,6 +114,12 @@ def loss_cases():
     b["K"][:, 2] = torch.tensor([1e-4, -2e-4, 1.05], dtype=torch.float64)
     cases["fullK_B3_N16"] = dict(b, valid=None, want_pts3d=True)
 
+    # cameras that are not a scaled rotation (synth.CAMERAS): the reference's real out_K = affine33 @ cam_K with LM-O's fy / fx and
+    # cx != cy, and a stretched + skewed one.  Every other case above has K[0,0] == K[1,1], K[0,1] == -K[1,0], K[0,2] == K[1,2]
+    for cam, seed in (("bop", 16), ("stress", 17)):
+        b = synth.make_batch(3, 16, seed=seed, dtype=torch.float64, camera=cam)
+        cases[f"{cam}K_B3_N16"] = dict(b, valid=None, want_pts3d=True)
+
     # minimal problem (N=3: six residual rows for six pose parameters).  N=2 is NOT a fixture: H is then rank-deficient and
     # the reference's own fp32 and fp64 paths disagree on whether cholesky_ex flags it (round-off decides: 16.98 vs 21.59)
     b = synth.make_batch(3, 3, seed=15, dtype=torch.float64)

@@ -30,12 +30,12 @@ def fixture_has_fp32_reference(path):
     return "noisefree" not in path
 
 
-def shape_inputs(B, N, seed, batch_seed=None, outlier_frac=0.05):
+def shape_inputs(B, N, seed, batch_seed=None, outlier_frac=0.05, camera="rot"):
     """CPU inputs of the shape tests: synth.make_batch, a seeded valid mask (about a fifth of the points out) and the narrow cotangent
-    `rand + 0.5` every loss test has used so far."""
+    `rand + 0.5` every loss test has used so far.  `camera`: synth.CAMERAS (tests/test_gpu_cameras.py)."""
     from lc_amd import synth
 
-    b = synth.make_batch(B, N, seed=seed if batch_seed is None else batch_seed, outlier_frac=outlier_frac)
+    b = synth.make_batch(B, N, seed=seed if batch_seed is None else batch_seed, outlier_frac=outlier_frac, camera=camera)
     g = torch.Generator().manual_seed(seed)
     valid = (torch.rand(B, N, generator=g) > 0.2).float()
     valid[:, :3] = 1

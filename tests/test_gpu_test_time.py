@@ -24,6 +24,11 @@ def _to(d, dev):
 
 @pytest.mark.parametrize("name,B", [("zlmo", 6), ("glmo", 8)])
 def test_test_time_path_stage_by_stage(name, B):
+    stage_by_stage(name, B)
+
+
+def stage_by_stage(name, B, camera="rot"):
+    """The comparison of the module docstring for one config; `camera`: synth.CAMERAS (tests/test_gpu_cameras.py runs it on "bop")."""
     from lc_amd import floatbits, synth
     from lc_amd.config import AttrDict
     from lc_amd.dense import dense_front_end_select, dense_front_end_with_visibility, dense_select
@@ -31,7 +36,7 @@ def test_test_time_path_stage_by_stage(name, B):
     from lc_amd.pnp import gpu_solver, pnp_ceres
     from oracle import dense_oracle, floatbits_oracle, p3p_ransac_oracle, pnp_oracle, select_oracle
 
-    cfg, gt_c, out_c = synth.test_time_inputs(name, B=B, seed=11)
+    cfg, gt_c, out_c = synth.test_time_inputs(name, B=B, seed=11, camera=camera)
     if name == "zlmo":
         out_c["msk_vis_logits"][1] = -9.0  # an object the network sees nothing of: nothing selected, 4 pseudo-random pad entries
     cfg = AttrDict(cfg)
