@@ -8,9 +8,13 @@
 //   * lc_pnp_ransac_kernel: one workgroup per pose, its rounds on separate wavefronts, points staged in LDS -- for batches that fill
 //     the chip with one workgroup per pose (or few points);
 //   * lc_ransac_{hypotheses,score,select}_kernel: three launches over a workspace that spread the points of one pose over the chip
-//     (further down; lc_ransac_score_select_kernel: scoring and selection as one launch, an option that measured slower).
-// Either form can also write the 'weighted-filtered' re-selection of test.py:129-133 (the winner's inliers compacted to the front of
-// their rows: lc_pnp_ransac_init4_f32), which the workgroup that writes the inlier mask does on the way.
+//     (further down; lc_ransac_score_select_kernel: scoring and selection as one launch, an option that measured slower).  Its four
+//     scoring kernels (score, score_wide, score_live, score_select) differ in the units they take and in the order of their memory
+//     requests; what they do with a chunk is ONE body: load_hyp32, stage_chunk, score_chunk.
+// Both are reached through lc_pnp_ransac_init5_f32 (with or without a workspace).  Either form can also write the 'weighted-filtered'
+// re-selection of test.py:129-133 (the winner's inliers compacted to the front of their rows), which the workgroup that writes the
+// inlier mask does on the way.  The per-point arithmetic exists twice: score_point (the single launch's scalar walk over its LDS tile)
+// and score_chunk (every other form); the (count, error, id) arg-max once (best_of_wave, best_of_waves).
 // OpenCV's RNG/EPnP cannot be reproduced bit for bit (and OpenCV is absent here: parity at this boundary is unpinned and outside the
 // metric); the contract kept is the role: a pose inside the LM basin of convergence plus an inlier set for
 // `weighted_filtered` (test.py:129-134); the kernels' own contract is pinned by oracle/p3p_ransac_oracle.py.
@@ -388,6 +392,27 @@ __device__ __forceinline__ void score_pair(const float (&R)[9], const float (&t)
 __device__ __forceinline__ bool better_hyp(int oc, float oe, int oh, int c, float e, int h) {
     return oc > c || (oc == c && (oe < e || (oe == e && oh < h)));
 }
+// Arg-max of that ordering over the workgroup, in two steps because the single launch hands its poses over between them: the best of
+// the wavefront's lanes (every lane leaves with it) ...
+__device__ __forceinline__ void best_of_wave(int& cnt, float& err, int& hyp) {
+    for (int m = 32; m >= 1; m >>= 1) {
+        const int oc = __shfl_xor(cnt, m, kWave), oh = __shfl_xor(hyp, m, kWave);
+        const float oe = __shfl_xor(err, m, kWave);
+        if (better_hyp(oc, oe, oh, cnt, err, hyp)) { cnt = oc; err = oe; hyp = oh; }
+    }
+}
+// ... then the best of the wavefronts' winners through LDS (one entry per wavefront; holds a barrier: called by every thread, every
+// thread leaves with the winner).  Returns the wavefront that held it.
+__device__ __forceinline__ int best_of_waves(int& cnt, float& err, int& hyp, int* wv_cnt, float* wv_err, int* wv_hyp) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    if (lane == 0) { wv_cnt[wave] = cnt; wv_err[wave] = err; wv_hyp[wave] = hyp; }
+    __syncthreads();
+    int ww = 0;
+    cnt = wv_cnt[0]; err = wv_err[0]; hyp = wv_hyp[0];
+    for (int w = 1; w < nwaves; ++w)
+        if (better_hyp(wv_cnt[w], wv_err[w], wv_hyp[w], cnt, err, hyp)) { cnt = wv_cnt[w]; err = wv_err[w]; hyp = wv_hyp[w]; ww = w; }
+    return ww;
+}
 
 
 // K^-1 of the upper-triangular-free 2x3 camera block: u = k0 X/Z + k1 Y/Z + k2, v = k3 X/Z + k4 Y/Z + k5 (row 2 of K is (0,0,1) as in
@@ -412,6 +437,14 @@ __device__ __forceinline__ float threshold_px(const RansacParams& p, int b) {
     if (!p.per_pose_divides) return v;
     return v > 0.f ? p.reproj_err / v : p.reproj_err;
 }
+// Squared inlier threshold of pose b in normalised coordinates: reprojectionError px / focal scale (sqrt|det K2|)
+__device__ __forceinline__ float threshold2(const RansacParams& p, int b, const CamInv& kin) {
+    const float thr_px = threshold_px(p, b);
+    const float thr = thr_px * (float)sqrt(fabs(kin.idet));
+    return thr * thr;
+}
+// Correspondences of pose b: its count, at most the row length (no counts: every row is full)
+__device__ __forceinline__ int pose_count(const RansacParams& p, int b) { return min(p.counts ? p.counts[b] : p.Nmax, p.Nmax); }
 
 __device__ __forceinline__ RowCopy selection_rows(const RansacParams& p) {
     return RowCopy{p.pts2d, p.sel_w, p.pts3d, p.sel_in_index, p.sel_pts2d, p.sel_w_out, p.sel_pts3d, p.sel_index, 0};
@@ -581,7 +614,7 @@ __global__ __launch_bounds__(64 * kRansacMaxWaves) void lc_pnp_ransac_kernel(con
     __shared__ float wv_err[kRansacMaxWaves];
     __shared__ ChunkCounts chunk_cnt;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthr = blockDim.x, nwaves = nthr >> 6;
-    const int n = min(p.counts ? p.counts[b] : p.Nmax, p.Nmax);
+    const int n = pose_count(p, b);
     const size_t base = (size_t)b * p.Nmax;
     unsigned char* mask = p.inlier_mask + base;
     zero_bytes(mask, 0, p.Nmax);
@@ -605,10 +638,7 @@ __global__ __launch_bounds__(64 * kRansacMaxWaves) void lc_pnp_ransac_kernel(con
         __syncthreads();
     };
     stage_tile(0);
-    // inlier threshold in normalised coordinates: reprojectionError px / focal scale (sqrt|det K2|)
-    const float thr_px = threshold_px(p, b);
-    const float thr = thr_px * (float)sqrt(fabs(kin.idet));
-    const float thr2 = thr * thr;
+    const float thr2 = threshold2(p, b, kin);
 
     int best_cnt = -1, best_hyp = 0;
     float best_err = INFINITY;
@@ -662,31 +692,20 @@ __global__ __launch_bounds__(64 * kRansacMaxWaves) void lc_pnp_ransac_kernel(con
             if (have) best = cand;
         }
     }
-    // arg-max over lanes, then over the waves: (count, -err, -hypothesis id)
+    // arg-max over lanes, then over the waves; every wavefront's winning lane leaves its pose for the workgroup in between
     int win_cnt = best_cnt, win_hyp = best_hyp;
     float win_err = best_err;
-    auto better = better_hyp;
-    for (int m = 32; m >= 1; m >>= 1) {
-        const int oc = __shfl_xor(win_cnt, m, kWave), oh = __shfl_xor(win_hyp, m, kWave);
-        const float oe = __shfl_xor(win_err, m, kWave);
-        if (better(oc, oe, oh, win_cnt, win_err, win_hyp)) { win_cnt = oc; win_err = oe; win_hyp = oh; }
-    }
+    best_of_wave(win_cnt, win_err, win_hyp);
     if (best_hyp == win_hyp && best_cnt == win_cnt && win_cnt >= 0) {
         for (int k = 0; k < 9; ++k) best_pose[wave][k] = best.R[k];
         for (int k = 0; k < 3; ++k) best_pose[wave][9 + k] = best.t[k];
     }
-    if (lane == 0) { wv_cnt[wave] = win_cnt; wv_err[wave] = win_err; wv_hyp[wave] = win_hyp; }
-    __syncthreads();
-    int ww = 0;
-    win_cnt = wv_cnt[0]; win_err = wv_err[0]; win_hyp = wv_hyp[0];
-    for (int w = 1; w < nwaves; ++w) {
-        if (better(wv_cnt[w], wv_err[w], wv_hyp[w], win_cnt, win_err, win_hyp)) { win_cnt = wv_cnt[w]; win_err = wv_err[w]; win_hyp = wv_hyp[w]; ww = w; }
-    }
+    const int ww = best_of_waves(win_cnt, win_err, win_hyp, wv_cnt, wv_err, wv_hyp);
     write_result(p, b, n, win_cnt >= 4, best_pose[ww], win_hyp, thr2, kin, chunk_cnt, load_batch(p, base, 0, n));
 }
 
 
-// ---- split form (lc_pnp_ransac_init3_f32): the same RANSAC as three launches over a caller-provided workspace ---------------------
+// ---- split form (lc_pnp_ransac_init5_f32 with a workspace): the same RANSAC as three launches over a caller-provided workspace ---------------------
 // The one-workgroup-per-pose kernel above keeps one pose on ONE compute unit: 64 objects x 150 hypotheses x 1000+ points use a
 // quarter of the chip, and every wavefront walks all points of its pose (1024 x ~22 VALU slots x 4 cycles = 38 us at best).  Here
 //   1. hypotheses: grid rounds x B, one lane per hypothesis: sample, P3P, fourth-point pick -> workspace (fp32 for scoring, fp64
@@ -730,7 +749,7 @@ __host__ __device__ inline RansacWorkspace carve_workspace(void* ws, int B, int 
 __global__ __launch_bounds__(kWave) void lc_ransac_hypotheses_kernel(const RansacParams p) {
     LC_P3P_STAMP(0);
     const int b = blockIdx.x / p.rounds, hyp = (blockIdx.x % p.rounds) * kWave + threadIdx.x;
-    const int n = min(p.counts ? p.counts[b] : p.Nmax, p.Nmax);
+    const int n = pose_count(p, b);
     const RansacWorkspace w = carve_workspace(p.workspace, p.B, p.Nmax, p.rounds);
     if (hyp == 0) w.arrived[b] = 0;  // the ticketed scoring launch that follows counts the pose's chunks from zero
     if (n < 4) return;  // the selection step flags the pose
@@ -759,41 +778,29 @@ __global__ __launch_bounds__(kWave) void lc_ransac_hypotheses_kernel(const Ransa
     LC_P3P_STAMP(6);
 }
 
-__global__ __launch_bounds__(kWave * kRansacMaxWaves) void lc_ransac_score_kernel(const RansacParams p) {
-    // One wavefront per (pose, chunk, round of 64 hypotheses); the four wavefronts of a workgroup are independent (own LDS slice, no
-    // barrier).  Structure of arrays: four consecutive points load as one 16-byte LDS read per coordinate, already paired for the
-    // packed math.
-    __shared__ __attribute__((aligned(16))) float lds[kRansacMaxWaves][5][kChunkPts];
-    const RansacWorkspace w = carve_workspace(p.workspace, p.B, p.Nmax, p.rounds);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long unit = (long long)blockIdx.x * kRansacMaxWaves + wave;
-    const int per_pose = w.C * p.rounds;
-    if (unit >= (long long)p.B * per_pose) return;
-    const int b = (int)(unit / per_pose), rem = (int)(unit % per_pose), c = rem / p.rounds, round = rem % p.rounds;  // neighbours share a chunk
-    float *sX = lds[wave][0], *sY = lds[wave][1], *sZ = lds[wave][2], *sU = lds[wave][3], *sV = lds[wave][4];
-    // Everything that does not depend on the pose's point count is requested first (the count itself, K, this lane's hypothesis,
-    // the chunk's points up to the padded row length): one memory round trip instead of three dependent ones.
-    const int i0 = c * kChunkPts, cap = max(0, min(kChunkPts, p.Nmax - i0));
-    const size_t base = (size_t)b * p.Nmax + i0;
+// ---- the chunk body of the four scoring kernels: a lane's hypothesis, a 64-point chunk staged in LDS, the hypothesis scored on it ----
+// Each kernel below is what is particular to it -- which (pose, chunk, round) units it takes, the order in which it requests memory,
+// where the partial goes -- around these three steps, so that the inlier test, the padding rule and the even / odd error association
+// that every launch form must agree on exist once.
+
+// Hypothesis `hyp` of pose b as the scoring reads it: R, t in fp32
+__device__ __forceinline__ void load_hyp32(const RansacWorkspace& w, int b, int hyp, float (&R)[9], float (&t)[3]) {
+    const float* h32 = w.hyp32 + 12 * ((size_t)b * w.H + hyp);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = h32[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = h32[9 + k];
+}
+
+__device__ __forceinline__ int padded_to_four(int cnt_pts) { return (cnt_pts + 3) & ~3; }
+
+// The calling wavefront's point of a chunk (gx, gy, gz; pixel gu, gv; lanes below cnt_pts hold one) -> five LDS rows of kChunkPts floats.
+// Structure of arrays: four consecutive points load as one 16-byte LDS read per coordinate, already paired for the packed math.
+// Returns the number of staged entries, cnt_pts rounded up to whole groups of four.  The caller places the barrier its form needs.
+__device__ __forceinline__ int stage_chunk(float* sX, float* sY, float* sZ, float* sU, float* sV, int lane, int cnt_pts, const CamInv& kin,
+                                           float gx, float gy, float gz, float gu, float gv) {
     static_assert(kChunkPts == kWave, "one point per lane");
-    const bool in_row = lane < cap;
-    const float gx = in_row ? p.pts3d[(base + lane) * 3] : 0.f, gy = in_row ? p.pts3d[(base + lane) * 3 + 1] : 0.f,
-                gz = in_row ? p.pts3d[(base + lane) * 3 + 2] : 0.f;
-    const float gu = in_row ? p.pts2d[(base + lane) * 2] : 0.f, gv = in_row ? p.pts2d[(base + lane) * 2 + 1] : 0.f;
-    const int hyp = round * kWave + lane;
-    float R[9], t[3];
-    {
-        const float* h32 = w.hyp32 + 12 * ((size_t)b * w.H + hyp);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) R[k] = h32[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) t[k] = h32[9 + k];
-    }
-    const CamInv kin(p.K + 9 * (size_t)b);
-    const int n = min(p.counts ? p.counts[b] : p.Nmax, p.Nmax);
-    if (n < 4) return;
-    const int cnt_pts = max(0, min(kChunkPts, n - i0)), cnt4 = (cnt_pts + 3) & ~3;
-    if (cnt_pts == 0) return;  // the selection step sums the chunks the pose has
+    const int cnt4 = padded_to_four(cnt_pts);
     if (lane < cnt_pts) {
         float ux, uy;
         kin.normalise(gu, gv, ux, uy);
@@ -803,15 +810,18 @@ __global__ __launch_bounds__(kWave * kRansacMaxWaves) void lc_ransac_score_kerne
         sX[lane] = sY[lane] = sZ[lane] = 0.f;
         sU[lane] = sV[lane] = -INFINITY;
     }
-    __builtin_amdgcn_wave_barrier();  // LDS operations of one wavefront execute in order: no wait beyond the compiler's own
-    const float thr_px = threshold_px(p, b);
-    const float thr = thr_px * (float)sqrt(fabs(kin.idet));
-    const float thr2 = thr * thr;
-    int cnt = 0;
-    v2f_t err2 = {0.f, 0.f};
+    return cnt4;
+}
+
+// The lane's hypothesis on the cnt4 staged entries -> the chunk's partial (pack_partial: inlier count, chunk_error of the even / odd sums)
+__device__ __forceinline__ unsigned long long score_chunk(const float (&R)[9], const float (&t)[3], const float* sX, const float* sY, const float* sZ,
+                                                          const float* sU, const float* sV, int cnt4, float thr2) {
     typedef float v4f_t __attribute__((ext_vector_type(4)));
     auto rd = [](const float* a, int i) { return *reinterpret_cast<const v4f_t*>(a + i); };
-    // two groups of four points per iteration, in two register sets: the LDS reads of one are in flight while the other is scored
+    int cnt = 0;
+    v2f_t err2 = {0.f, 0.f};
+    // two groups of four points per iteration, in two register sets: the LDS reads of one are in flight while the other is scored (with one
+    // set the compiler rotates the loop and every iteration waits out its own reads).  cnt4 is wave-uniform: a scalar loop.
     const int last = __builtin_amdgcn_readfirstlane(cnt4) - 4;
     v4f_t X = rd(sX, 0), Y = rd(sY, 0), Z = rd(sZ, 0), U = rd(sU, 0), V = rd(sV, 0);
     for (int i = 0; i <= last; i += 8) {
@@ -825,8 +835,41 @@ __global__ __launch_bounds__(kWave * kRansacMaxWaves) void lc_ransac_score_kerne
             score_pair(R, t, X1.zw, Y1.zw, Z1.zw, U1.zw, V1.zw, thr2, cnt, err2);
         }
     }
+    return pack_partial(cnt, chunk_error(err2.x, err2.y, t[2]));
+}
+
+__global__ __launch_bounds__(kWave * kRansacMaxWaves) void lc_ransac_score_kernel(const RansacParams p) {
+    // One wavefront per (pose, chunk, round of 64 hypotheses); the four wavefronts of a workgroup are independent (own LDS slice, no
+    // barrier).
+    __shared__ __attribute__((aligned(16))) float lds[kRansacMaxWaves][5][kChunkPts];
+    const RansacWorkspace w = carve_workspace(p.workspace, p.B, p.Nmax, p.rounds);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long unit = (long long)blockIdx.x * kRansacMaxWaves + wave;
+    const int per_pose = w.C * p.rounds;
+    if (unit >= (long long)p.B * per_pose) return;
+    const int b = (int)(unit / per_pose), rem = (int)(unit % per_pose), c = rem / p.rounds, round = rem % p.rounds;  // neighbours share a chunk
+    float *sX = lds[wave][0], *sY = lds[wave][1], *sZ = lds[wave][2], *sU = lds[wave][3], *sV = lds[wave][4];
+    // Everything that does not depend on the pose's point count is requested first (the count itself, K, this lane's hypothesis,
+    // the chunk's points up to the padded row length): one memory round trip instead of three dependent ones.
+    const int i0 = c * kChunkPts, cap = max(0, min(kChunkPts, p.Nmax - i0));
+    const size_t base = (size_t)b * p.Nmax + i0;
+    const bool in_row = lane < cap;
+    const float gx = in_row ? p.pts3d[(base + lane) * 3] : 0.f, gy = in_row ? p.pts3d[(base + lane) * 3 + 1] : 0.f,
+                gz = in_row ? p.pts3d[(base + lane) * 3 + 2] : 0.f;
+    const float gu = in_row ? p.pts2d[(base + lane) * 2] : 0.f, gv = in_row ? p.pts2d[(base + lane) * 2 + 1] : 0.f;
+    const int hyp = round * kWave + lane;
+    float R[9], t[3];
+    load_hyp32(w, b, hyp, R, t);
+    const CamInv kin(p.K + 9 * (size_t)b);
+    const int n = pose_count(p, b);
+    if (n < 4) return;
+    const int cnt_pts = max(0, min(kChunkPts, n - i0));
+    if (cnt_pts == 0) return;  // the selection step sums the chunks the pose has
+    const int cnt4 = stage_chunk(sX, sY, sZ, sU, sV, lane, cnt_pts, kin, gx, gy, gz, gu, gv);
+    __builtin_amdgcn_wave_barrier();  // LDS operations of one wavefront execute in order: no wait beyond the compiler's own
+    const float thr2 = threshold2(p, b, kin);
     const size_t o = ((size_t)b * w.C + c) * w.H + hyp;
-    w.part[o] = pack_partial(cnt, chunk_error(err2.x, err2.y, t[2]));
+    w.part[o] = score_chunk(R, t, sX, sY, sZ, sU, sV, cnt4, thr2);
 }
 
 // Rows wider than 4096 candidates (zlmo's test-time shape: 16 384 per object, of which a pose's count keeps a fifth): one wavefront per
@@ -847,7 +890,7 @@ __global__ __launch_bounds__(kWave * kRansacMaxWaves) void lc_ransac_score_wide_
     const int groups = (w.C + kWideGroup - 1) / kWideGroup, per_pose = groups * p.rounds;
     if (unit >= (long long)p.B * per_pose) return;
     const int b = (int)(unit / per_pose), rem = (int)(unit % per_pose), c0 = (rem / p.rounds) * kWideGroup, round = rem % p.rounds;
-    const int n = min(p.counts ? p.counts[b] : p.Nmax, p.Nmax);
+    const int n = pose_count(p, b);
     if (n < 4 || c0 * kChunkPts >= n) return;
     const int c1 = min(min(c0 + kWideGroup, w.C), (n + kChunkPts - 1) / kChunkPts);  // chunks [c0, c1) of this pose exist
     float *sX = lds[wave][0], *sY = lds[wave][1], *sZ = lds[wave][2], *sU = lds[wave][3], *sV = lds[wave][4];
@@ -860,50 +903,14 @@ __global__ __launch_bounds__(kWave * kRansacMaxWaves) void lc_ransac_score_wide_
     Pt cur = fetch(c0);
     const int hyp = round * kWave + lane;
     float R[9], t[3];
-    {
-        const float* h32 = w.hyp32 + 12 * ((size_t)b * w.H + hyp);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) R[k] = h32[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) t[k] = h32[9 + k];
-    }
+    load_hyp32(w, b, hyp, R, t);
     const CamInv kin(p.K + 9 * (size_t)b);
-    const float thr_px = threshold_px(p, b);
-    const float thr = thr_px * (float)sqrt(fabs(kin.idet));
-    const float thr2 = thr * thr;
-    typedef float v4f_t __attribute__((ext_vector_type(4)));
-    auto rd = [](const float* a, int i) { return *reinterpret_cast<const v4f_t*>(a + i); };
+    const float thr2 = threshold2(p, b, kin);
     for (int c = c0; c < c1; ++c) {
         const Pt nxt = fetch(c + 1 < c1 ? c + 1 : c);  // branch-free: the last iteration re-requests its own chunk (a cache hit)
-        const int i0 = c * kChunkPts, cnt_pts = min(kChunkPts, n - i0), cnt4 = (cnt_pts + 3) & ~3;
-        if (lane < cnt_pts) {
-            float ux, uy;
-            kin.normalise(cur.u, cur.v, ux, uy);
-            sU[lane] = -ux; sV[lane] = -uy;
-            sX[lane] = cur.x; sY[lane] = cur.y; sZ[lane] = cur.z;
-        } else if (lane < cnt4) {
-            sX[lane] = sY[lane] = sZ[lane] = 0.f;
-            sU[lane] = sV[lane] = -INFINITY;
-        }
+        const int cnt4 = stage_chunk(sX, sY, sZ, sU, sV, lane, min(kChunkPts, n - c * kChunkPts), kin, cur.x, cur.y, cur.z, cur.u, cur.v);
         __builtin_amdgcn_wave_barrier();
-        int cnt = 0;
-        v2f_t err2 = {0.f, 0.f};
-        // two groups of four points per iteration, in two register sets: the LDS reads of one are in flight while the other is scored (with one
-        // set the compiler rotates the loop and every iteration waits out its own reads).  cnt4 is wave-uniform: a scalar loop.
-        const int last = __builtin_amdgcn_readfirstlane(cnt4) - 4;
-        v4f_t X = rd(sX, 0), Y = rd(sY, 0), Z = rd(sZ, 0), U = rd(sU, 0), V = rd(sV, 0);
-        for (int i = 0; i <= last; i += 8) {
-            const int i1 = min(i + 4, last), i2 = min(i + 8, last);
-            const v4f_t X1 = rd(sX, i1), Y1 = rd(sY, i1), Z1 = rd(sZ, i1), U1 = rd(sU, i1), V1 = rd(sV, i1);
-            score_pair(R, t, X.xy, Y.xy, Z.xy, U.xy, V.xy, thr2, cnt, err2);
-            score_pair(R, t, X.zw, Y.zw, Z.zw, U.zw, V.zw, thr2, cnt, err2);
-            X = rd(sX, i2); Y = rd(sY, i2); Z = rd(sZ, i2); U = rd(sU, i2); V = rd(sV, i2);
-            if (i + 4 <= last) {  // uniform
-                score_pair(R, t, X1.xy, Y1.xy, Z1.xy, U1.xy, V1.xy, thr2, cnt, err2);
-                score_pair(R, t, X1.zw, Y1.zw, Z1.zw, U1.zw, V1.zw, thr2, cnt, err2);
-            }
-        }
-        w.part[((size_t)b * w.C + c) * w.H + hyp] = pack_partial(cnt, chunk_error(err2.x, err2.y, t[2]));
+        w.part[((size_t)b * w.C + c) * w.H + hyp] = score_chunk(R, t, sX, sY, sZ, sU, sV, cnt4, thr2);
         __builtin_amdgcn_wave_barrier();  // the chunk's LDS reads precede the next chunk's writes (one wavefront: program order)
         cur = nxt;
     }
@@ -924,7 +931,7 @@ __global__ __launch_bounds__(kWave * kRansacMaxWaves) void lc_ransac_score_live_
     const RansacWorkspace w = carve_workspace(p.workspace, p.B, p.Nmax, p.rounds);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int first = (int)blockIdx.x * kRansacMaxWaves + wave, stride = (int)gridDim.x * kRansacMaxWaves;
-    auto count_of = [&](int b) { return b < p.B ? min(p.counts ? p.counts[b] : p.Nmax, p.Nmax) : 0; };
+    auto count_of = [&](int b) { return b < p.B ? pose_count(p, b) : 0; };
     const int n_lo = count_of(lane), n_hi = count_of(lane + kWave);
     auto units_of = [&](int n) { return n >= 4 ? ((n + kChunkPts - 1) / kChunkPts) * p.rounds : 0; };
     int incl_lo = units_of(n_lo), incl_hi = units_of(n_hi);  // -> inclusive prefixes in pose order (poses 0..63, then 64..127)
@@ -936,8 +943,6 @@ __global__ __launch_bounds__(kWave * kRansacMaxWaves) void lc_ransac_score_live_
     incl_hi += __shfl(incl_lo, kWave - 1, kWave);
     const int live = __shfl(incl_hi, kWave - 1, kWave);
     float *sX = lds[wave][0], *sY = lds[wave][1], *sZ = lds[wave][2], *sU = lds[wave][3], *sV = lds[wave][4];
-    typedef float v4f_t __attribute__((ext_vector_type(4)));
-    auto rd = [](const float* a, int i) { return *reinterpret_cast<const v4f_t*>(a + i); };
     for (int u = first; u < live; u += stride) {  // wave-uniform
         // the pose whose units hold u: the first whose inclusive prefix exceeds it (poses without units share their predecessor's prefix)
         const int b = __builtin_amdgcn_readfirstlane(__popcll(__ballot(incl_lo <= u)) + __popcll(__ballot(incl_hi <= u)));
@@ -948,44 +953,12 @@ __global__ __launch_bounds__(kWave * kRansacMaxWaves) void lc_ransac_score_live_
         const float gx = p.pts3d[i * 3], gy = p.pts3d[i * 3 + 1], gz = p.pts3d[i * 3 + 2], gu = p.pts2d[i * 2], gv = p.pts2d[i * 2 + 1];
         const int hyp = round * kWave + lane;
         float R[9], t[3];
-        {
-            const float* h32 = w.hyp32 + 12 * ((size_t)b * w.H + hyp);
-#pragma unroll
-            for (int k = 0; k < 9; ++k) R[k] = h32[k];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) t[k] = h32[9 + k];
-        }
+        load_hyp32(w, b, hyp, R, t);
         const CamInv kin(p.K + 9 * (size_t)b);
-        const float thr_px = threshold_px(p, b);
-        const float thr = thr_px * (float)sqrt(fabs(kin.idet));
-        const float thr2 = thr * thr;
-        const int i0 = c * kChunkPts, cnt_pts = min(kChunkPts, n - i0), cnt4 = (cnt_pts + 3) & ~3;
-        if (lane < cnt_pts) {
-            float ux, uy;
-            kin.normalise(gu, gv, ux, uy);
-            sU[lane] = -ux; sV[lane] = -uy;
-            sX[lane] = gx; sY[lane] = gy; sZ[lane] = gz;
-        } else if (lane < cnt4) {
-            sX[lane] = sY[lane] = sZ[lane] = 0.f;
-            sU[lane] = sV[lane] = -INFINITY;
-        }
+        const float thr2 = threshold2(p, b, kin);
+        const int cnt4 = stage_chunk(sX, sY, sZ, sU, sV, lane, min(kChunkPts, n - c * kChunkPts), kin, gx, gy, gz, gu, gv);
         __builtin_amdgcn_wave_barrier();
-        int cnt = 0;
-        v2f_t err2 = {0.f, 0.f};
-        const int last = __builtin_amdgcn_readfirstlane(cnt4) - 4;
-        v4f_t X = rd(sX, 0), Y = rd(sY, 0), Z = rd(sZ, 0), U = rd(sU, 0), V = rd(sV, 0);
-        for (int j = 0; j <= last; j += 8) {
-            const int j1 = min(j + 4, last), j2 = min(j + 8, last);
-            const v4f_t X1 = rd(sX, j1), Y1 = rd(sY, j1), Z1 = rd(sZ, j1), U1 = rd(sU, j1), V1 = rd(sV, j1);
-            score_pair(R, t, X.xy, Y.xy, Z.xy, U.xy, V.xy, thr2, cnt, err2);
-            score_pair(R, t, X.zw, Y.zw, Z.zw, U.zw, V.zw, thr2, cnt, err2);
-            X = rd(sX, j2); Y = rd(sY, j2); Z = rd(sZ, j2); U = rd(sU, j2); V = rd(sV, j2);
-            if (j + 4 <= last) {  // uniform
-                score_pair(R, t, X1.xy, Y1.xy, Z1.xy, U1.xy, V1.xy, thr2, cnt, err2);
-                score_pair(R, t, X1.zw, Y1.zw, Z1.zw, U1.zw, V1.zw, thr2, cnt, err2);
-            }
-        }
-        w.part[((size_t)b * w.C + c) * w.H + hyp] = pack_partial(cnt, chunk_error(err2.x, err2.y, t[2]));
+        w.part[((size_t)b * w.C + c) * w.H + hyp] = score_chunk(R, t, sX, sY, sZ, sU, sV, cnt4, thr2);
         __builtin_amdgcn_wave_barrier();  // the unit's LDS reads precede the next unit's writes (one wavefront: program order)
     }
 }
@@ -1002,7 +975,7 @@ struct SelectShared {
 };
 template <bool XCD, int kFirstChunks = 32>
 __device__ __forceinline__ void select_winner(const RansacParams& p, const RansacWorkspace& w, int b, SelectShared& sh) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthr = blockDim.x, nwaves = nthr >> 6;
+    const int tid = threadIdx.x, nthr = blockDim.x;
     auto part_at = [&](size_t o) { return XCD ? xcd_load(w.part + o) : w.part[o]; };
     int win_cnt = -1, win_hyp = 0x7fffffff;
     float win_err = INFINITY;
@@ -1012,7 +985,7 @@ __device__ __forceinline__ void select_winner(const RansacParams& p, const Ransa
     // chunk rows and all four batch slots requested blindly, ~30 this way): the first batch of the pose's correspondences (the
     // inlier mask below needs them), this thread's own hypothesis in double precision (the winner's is the answer: its thread hands
     // it over through LDS instead of a dependent load), the chunk partials of this thread's first hypothesis.
-    const int n = min(p.counts ? p.counts[b] : p.Nmax, p.Nmax);
+    const int n = pose_count(p, b);
     const int chunks = n >= 4 ? (n + kChunkPts - 1) / kChunkPts : 0;
     double2 mine[6];
     {
@@ -1065,16 +1038,8 @@ __device__ __forceinline__ void select_winner(const RansacParams& p, const Ransa
         }
         if (better_hyp(cnt, err, hyp, win_cnt, win_err, win_hyp)) { win_cnt = cnt; win_err = err; win_hyp = hyp; }
     }
-    for (int m = 32; m >= 1; m >>= 1) {
-        const int oc = __shfl_xor(win_cnt, m, kWave), oh = __shfl_xor(win_hyp, m, kWave);
-        const float oe = __shfl_xor(win_err, m, kWave);
-        if (better_hyp(oc, oe, oh, win_cnt, win_err, win_hyp)) { win_cnt = oc; win_err = oe; win_hyp = oh; }
-    }
-    if (lane == 0) { sh.wv_cnt[wave] = win_cnt; sh.wv_err[wave] = win_err; sh.wv_hyp[wave] = win_hyp; }
-    __syncthreads();
-    win_cnt = sh.wv_cnt[0]; win_err = sh.wv_err[0]; win_hyp = sh.wv_hyp[0];
-    for (int v = 1; v < nwaves; ++v)
-        if (better_hyp(sh.wv_cnt[v], sh.wv_err[v], sh.wv_hyp[v], win_cnt, win_err, win_hyp)) { win_cnt = sh.wv_cnt[v]; win_err = sh.wv_err[v]; win_hyp = sh.wv_hyp[v]; }
+    best_of_wave(win_cnt, win_err, win_hyp);
+    best_of_waves(win_cnt, win_err, win_hyp, sh.wv_cnt, sh.wv_err, sh.wv_hyp);
     const bool ok = win_cnt >= 4;
     LC_SEL_STAMP(2);
     if (ok) {
@@ -1087,10 +1052,9 @@ __device__ __forceinline__ void select_winner(const RansacParams& p, const Ransa
         }
     }
     __syncthreads();
-    const float thr_px = threshold_px(p, b);
-    const float thr = thr_px * (float)sqrt(fabs(kin.idet));
+    const float thr2 = threshold2(p, b, kin);
     LC_SEL_STAMP(3);
-    write_result(p, b, n, ok, sh.best_pose, win_hyp, thr * thr, kin, sh.chunk_cnt, first);
+    write_result(p, b, n, ok, sh.best_pose, win_hyp, thr2, kin, sh.chunk_cnt, first);
     LC_SEL_STAMP(6);
 }
 
@@ -1105,7 +1069,7 @@ __global__ __launch_bounds__(kWave * kSelMaxWaves) void lc_ransac_select_wide_ke
     select_winner<false, 8>(p, carve_workspace(p.workspace, p.B, p.Nmax, p.rounds), blockIdx.x, sh);
 }
 
-// Ticketed form (lc_pnp_ransac_init4_f32 with `ticketed`): scoring AND selection in one launch.  One workgroup per (pose, chunk of 64 points), its
+// Ticketed form (lc_pnp_ransac_init5_f32 with `ticketed`): scoring AND selection in one launch.  One workgroup per (pose, chunk of 64 points), its
 // wavefronts take the rounds of 64 hypotheses; the chunk's partials are written through the caches, the workgroup counts itself
 // in, and the workgroup that completes the pose's count runs the selection -- nobody waits, so no co-residency is assumed, and the
 // partials are still summed in chunk order: same results as the three launches.  Saves the selection launch and its boundary --
@@ -1129,15 +1093,9 @@ __global__ __launch_bounds__(kWave * kRansacMaxWaves) void lc_ransac_score_selec
                 gz = in_row ? p.pts3d[(base + lane) * 3 + 2] : 0.f;
     const float gu = in_row ? p.pts2d[(base + lane) * 2] : 0.f, gv = in_row ? p.pts2d[(base + lane) * 2 + 1] : 0.f;
     float R[9], t[3];
-    {
-        const float* h32 = w.hyp32 + 12 * ((size_t)b * w.H + min(wave, p.rounds - 1) * kWave + lane);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) R[k] = h32[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) t[k] = h32[9 + k];
-    }
+    load_hyp32(w, b, min(wave, p.rounds - 1) * kWave + lane, R, t);  // the wavefront's first round (one that exists, for a wavefront without a round)
     const CamInv kin(p.K + 9 * (size_t)b);
-    const int n = min(p.counts ? p.counts[b] : p.Nmax, p.Nmax);
+    const int n = pose_count(p, b);
     if (n < 4) {  // nothing was scored: chunk 0's workgroup flags the pose
         if (c == 0) {
             unsigned char* mask = p.inlier_mask + (size_t)b * p.Nmax;
@@ -1147,46 +1105,16 @@ __global__ __launch_bounds__(kWave * kRansacMaxWaves) void lc_ransac_score_selec
         return;
     }
     const int chunks = (n + kChunkPts - 1) / kChunkPts;
-    const int cnt_pts = max(0, min(kChunkPts, n - i0)), cnt4 = (cnt_pts + 3) & ~3;
+    const int cnt_pts = max(0, min(kChunkPts, n - i0)), cnt4 = padded_to_four(cnt_pts);
     if (cnt_pts == 0) return;  // a chunk the pose does not have: not counted
-    if (wave == 0) {
-        if (lane < cnt_pts) {
-            float ux, uy;
-            kin.normalise(gu, gv, ux, uy);
-            sU[lane] = -ux; sV[lane] = -uy;
-            sX[lane] = gx; sY[lane] = gy; sZ[lane] = gz;
-        } else if (lane < cnt4) {
-            sX[lane] = sY[lane] = sZ[lane] = 0.f;
-            sU[lane] = sV[lane] = -INFINITY;
-        }
-    }
+    if (wave == 0) stage_chunk(sX, sY, sZ, sU, sV, lane, cnt_pts, kin, gx, gy, gz, gu, gv);  // one slice for the workgroup
     __syncthreads();
-    const float thr_px = threshold_px(p, b);
-    const float thr = thr_px * (float)sqrt(fabs(kin.idet));
-    const float thr2 = thr * thr;
-    typedef float v4f_t __attribute__((ext_vector_type(4)));
-    auto rd = [](const float* a, int i) { return *reinterpret_cast<const v4f_t*>(a + i); };
+    const float thr2 = threshold2(p, b, kin);
     for (int round = wave; round < p.rounds; round += nwaves) {
         const int hyp = round * kWave + lane;
-        if (round != wave) {
-            const float* h32 = w.hyp32 + 12 * ((size_t)b * w.H + hyp);
-#pragma unroll
-            for (int k = 0; k < 9; ++k) R[k] = h32[k];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) t[k] = h32[9 + k];
-        }
-        int cnt = 0;
-        v2f_t err2 = {0.f, 0.f};
-        v4f_t X = rd(sX, 0), Y = rd(sY, 0), Z = rd(sZ, 0), U = rd(sU, 0), V = rd(sV, 0);
-        for (int i = 0; i < cnt4; i += 4) {
-            const int nx = i + 4 < cnt4 ? i + 4 : i;
-            const v4f_t Xn = rd(sX, nx), Yn = rd(sY, nx), Zn = rd(sZ, nx), Un = rd(sU, nx), Vn = rd(sV, nx);
-            score_pair(R, t, X.xy, Y.xy, Z.xy, U.xy, V.xy, thr2, cnt, err2);
-            score_pair(R, t, X.zw, Y.zw, Z.zw, U.zw, V.zw, thr2, cnt, err2);
-            X = Xn; Y = Yn; Z = Zn; U = Un; V = Vn;
-        }
+        if (round != wave) load_hyp32(w, b, hyp, R, t);
         const size_t o = ((size_t)b * w.C + c) * w.H + hyp;
-        xcd_store(w.part + o, pack_partial(cnt, chunk_error(err2.x, err2.y, t[2])));
+        xcd_store(w.part + o, score_chunk(R, t, sX, sY, sZ, sU, sV, cnt4, thr2));
     }
     xcd_stores_done();
     __syncthreads();  // every wave's partials have been acknowledged

@@ -91,6 +91,30 @@ def test_split_form_equals_single_launch(B, N, iters, noise):
         assert torch.equal(x, y)
 
 
+@pytest.mark.parametrize("B,N,iters,first", [(128, 128, 150, 1), (64, 4160, 64, 4097), (130, 4160, 64, 4097)],
+                         ids=["one_chunk_units", "live_units", "wide_groups"])
+def test_every_tail_length_of_the_last_chunk_in_every_form(B, N, iters, first):
+    """The chunk body the scoring kernels share, at every length of a pose's last 64-point chunk (the pad-to-four rule and the loop's
+    last / i1 / i2 indexing): counts first, first + 1, ... (64 of them in turn), split form == single launch == ticketed form, bit for bit.
+    (128, 128): counts 1..128 -- 1..3 invalid in every form, a first chunk of 4..64 and a second of 1..64 points, lc_ransac_score_kernel.
+    (64, 4160): 65 chunks, the last of 1..64 points, one round (fewer than the workgroup's wavefronts): lc_ransac_score_live_kernel and
+    lc_ransac_select_wide_kernel.  (130, 4160): the same rows for more than 128 poses: lc_ransac_score_wide_kernel."""
+    from lc_amd import synth
+    from lc_amd.pnp import gpu_solver
+
+    dev = torch.device("cuda:0")
+    b = {k: v.to(dev) for k, v in synth.make_batch(B, N, seed=B + N, outlier_frac=0.3, noise_px=0.7).items()}
+    counts = (first + torch.arange(B) % (64 if first > 1 else B)).to(torch.int32)
+    assert int(counts.max()) <= N and len(set((counts % 64).tolist())) == 64  # every tail length
+    split, single, ticketed = [gpu_solver.solve_device(b["K"], b["pts3d"], b["pts2d"], counts, reprojectionError=2.0, iterations=iters, seed=11,
+                                                       refine=False, return_hypothesis=True, split=s, ticketed=t)
+                               for s, t in ((True, False), (False, False), (True, True))]
+    assert bool(split[2].cpu()[counts < 4].all()) and not bool(split[2].all())  # too few correspondences: invalid (in every form, below)
+    for other, name in ((single, "single launch"), (ticketed, "ticketed")):
+        for x, y, what in zip(other, split, ("states", "inlier masks", "invalid flags", "winning hypothesis", "inlier counts")):
+            assert torch.equal(x, y), (name, what, (x != y).nonzero()[:8].tolist())
+
+
 @pytest.mark.parametrize("split,ticketed", [(True, False), (True, True), (False, False)], ids=["split", "split_ticketed", "single_launch"])
 @pytest.mark.parametrize("B,N,iters,min_count", [(64, 1024, 150, 4), (5, 300, 64, 4), (3, 2500, 200, 6), (40, 64, 150, 4), (7, 129, 150, 4),
                                                  (3, 6000, 150, 4)])
