@@ -71,7 +71,8 @@ __device__ __forceinline__ int block_sum_open(int lane) {
     wave_sync();  // the previous totals have been read
     return lane + 2 * (lane >> 5);
 }
-__device__ __forceinline__ void block_sum_put(double* lds, int pos, int k, double v) { lds[k * 68 + pos] = v; }
+template <int ROW = 68>  // doubles between the rows of two entries (the team form has its own, kTeamRowDoubles below)
+__device__ __forceinline__ void block_sum_put(double* lds, int pos, int k, double v) { lds[k * ROW + pos] = v; }
 
 // sum of one 32-double segment of a row (sixteen 16-byte reads): the order every form of the LDS block sum adds a segment in
 __device__ __forceinline__ double block_sum_segment(const double2* row) {
@@ -90,6 +91,23 @@ __device__ __forceinline__ double block_sum_segment(const double2* row) {
         for (int i = 0; i < st; ++i) { a[i].x += a[i + st].x; a[i].y += a[i + st].y; }
     }
     return a[0].x + a[0].y;
+}
+// One COMPONENT of that tree, for a segment dealt to two lanes: block_sum_segment adds the 32 doubles d[0..31] of a segment as
+// d[j] + d[j + 16], then + 8, + 4, + 2 (a[i] += a[i + st] on 16-byte pairs), and only its last add, d[0] + d[1], joins an even-indexed
+// double (.x of a pair) with an odd-indexed one (.y).  This is everything before that add for the 16 doubles of one parity -- `d` points at
+// the segment's double 0 (.x) or 1 (.y) -- in the same order; the caller's x + y is block_sum_segment's total bit for bit.
+__device__ __forceinline__ double block_sum_segment_component(const double* d) {
+    double a[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = d[2 * i];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] += d[16 + 2 * i];
+#pragma unroll
+    for (int st = 4; st >= 1; st >>= 1) {
+#pragma unroll
+        for (int i = 0; i < st; ++i) a[i] += a[i + st];
+    }
+    return a[0];
 }
 
 template <int K>
@@ -135,24 +153,38 @@ __device__ __forceinline__ void arrival_reset(unsigned* words, int tid) {
 
 // The one-wave sum played by a TEAM of two wavefronts that both hold all 64 values of every entry (lane = point in both:
 // the pose unit's latency build, where half the SIMDs idle next to a wave that is bound by instruction issue).  Wave W produces and
-// stores only the entries k with k % 2 == W -- block_sum_put into the slots of the one-wave form -- and sums them itself: lane
-// l < K takes segment l % 2 of entry 2 (l / 2) + W with the instruction sequence of block_sum_close<K>, so every total has the
-// one-wave form's bits.  A wave's rows are written and read by that wave alone (DS operations of a wave execute in program order: no
+// stores only the entries k with k % 2 == W -- block_sum_put<kTeamRowDoubles>, the slots of the one-wave form in rows of the team's own
+// stride -- and sums them itself on 2 K lanes: lane l takes component l % 2 (.x / .y of the 16-byte pairs) of segment (l / 2) % 2 of
+// entry 2 (l / 4) + W, 15 adds where a lane with a whole segment issues 31 (a VALU instruction costs the same for any number of active
+// lanes).  One quad exchange joins the components -- block_sum_segment's last add, a[0].x + a[0].y -- and a second one the two
+// segments, as block_sum_close<K> joins them: every total has the one-wave form's bits.
+// LDS banks: the component reads are 8-byte reads of stride 16 bytes (the compiler pairs them into ds_read2_b64: banks (a / 4) % 32,
+// groups of 16 consecutive lanes, i.e. four entries; a lone ds_read_b64: % 64, 32 lanes, eight entries).  The four lanes of an entry start
+// 0, 2, 4 and 6 dwords into its row (34 doubles between the segments = 4 dwords mod 64) and cover 8 consecutive banks, so the rows of
+// consecutive entries OF ONE WAVE, 2 kTeamRowDoubles doubles apart, must start an odd multiple of 8 dwords apart: kTeamRowDoubles = 2,
+// 6, 10 or 14 mod 16.  66 is the smallest that holds the 32 + 2 + 32 doubles of a row; the one-wave form's 68 puts entries q and q + 2 of
+// a group on the same banks (2-way; measured: profiles/teamsum/NOTES.md).  The stores (lane t at t + 2 (t / 32), 16 lanes = 32
+// consecutive dwords) are conflict-free at any row stride.
+// A wave's rows are written and read by that wave alone (DS operations of a wave execute in program order: no
 // barrier between its stores and its reads); the K / 2 totals of each wave meet in one of TWO rows of totals behind the slots, then
 // ONE workgroup barrier, then every thread of both waves reads all K.  The rows alternate by `phase` (toggled by the call, as in
 // block_sum_waves4): a wave still reading the totals of sum e is not overwritten by sum e + 1, and whoever writes sum e + 2 has
 // passed the barrier of e + 1, which the other wave only reaches with its reads of e done.  lds: sum_team2_lds_doubles(K) doubles.
-constexpr int sum_team2_lds_doubles(int K) { return K * 68 + 2 * K; }
+constexpr int kTeamRowDoubles = 66;
+static_assert(kTeamRowDoubles >= 66 && kTeamRowDoubles % 4 == 2, "a row holds two padded segments; rows of one wave fall on different banks");
+constexpr int sum_team2_lds_doubles(int K) { return K * kTeamRowDoubles + 2 * K; }
 template <int K, int W>
 __device__ __forceinline__ void block_sum_team2(double (&v)[K], double* lds, int lane, int& phase) {
     static_assert(K % 2 == 0 && K <= 32 && (W == 0 || W == 1), "an even number of entries dealt to two waves");
     wave_sync();  // this wave's stores are in its LDS queue
     double s = 0;
-    if (lane < K) s = block_sum_segment(reinterpret_cast<const double2*>(lds + (2 * (lane / 2) + W) * 68 + 34 * (lane % 2)));
-    s += dpp_mov_f64<kDppQuadXor1>(s, s);
-    double* tot = lds + K * 68 + K * phase;
+    const int comp = lane & 1, seg = (lane >> 1) & 1, entry = 2 * (lane >> 2) + W;
+    if (lane < 2 * K) s = block_sum_segment_component(lds + entry * kTeamRowDoubles + 34 * seg + comp);
+    s += dpp_mov_f64<kDppQuadXor1>(s, s);  // .x + .y (the .y lane: .y + .x, the same bits)
+    s += dpp_mov_f64<kDppQuadXor2>(s, s);  // segment 0 + segment 1
+    double* tot = lds + K * kTeamRowDoubles + K * phase;
     phase ^= 1;
-    if (lane < K && (lane % 2) == 0) tot[lane + W] = s;  // entry 2 (lane / 2) + W
+    if (lane < 2 * K && (lane % 4) == 0) tot[entry] = s;  // the lane whose adds were x + y, then segment 0 + segment 1
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < K; ++k) v[k] = tot[k];

@@ -57,7 +57,7 @@ namespace pnp {
 
 template <int NW>
 constexpr int kPnpLdsDoubles = [] { static_assert(NW == 1, "the four-wave kernels: kPnpWideReservedLdsDoubles"); return block_sum_lds_doubles(28); }();  // block_sum_close<28>
-constexpr int kPnpTeamLdsDoubles = sum_team2_lds_doubles(28);  // block_sum_team2<28>: the one-wave slots and a second row of totals
+constexpr int kPnpTeamLdsDoubles = sum_team2_lds_doubles(28);  // block_sum_team2<28>: the one-wave slots in rows of kTeamRowDoubles and a second row of totals
 // Static LDS of the four-wave kernels: 7 644 doubles (61 KB) are RESERVED -- the size of a slot per thread and entry -- where
 // block_sum_waves4 touches 192 doubles (block_sum_split: 194, in the split kernels' own array).  The size is in the kernel descriptor
 // and decides how many workgroups share a compute unit, so shrinking it changes the speed and wants a measurement: kept to the byte
@@ -143,25 +143,26 @@ __device__ __forceinline__ void accumulate_point(const Point& pt, const Rot& rt,
     }
     static_assert(PAR < 0 || STREAM, "entries are dealt by parity where they go to their LDS slots");
     constexpr auto mine = [](int k) { return PAR < 0 || (k & 1) == PAR; };  // (folds once the loops are unrolled)
+    constexpr int kRow = PAR < 0 ? 68 : kTeamRowDoubles;                    // the team's LDS rows have their own stride (block_sum_team2)
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
 #pragma unroll
         for (int j = i; j < 6; ++j) {
             if (mine(tri6(i, j))) {
                 const double v = __builtin_fma(J[0][i], J[0][j], J[1][i] * J[1][j]);
-                if constexpr (STREAM) block_sum_put(lds, pos, tri6(i, j), v);
+                if constexpr (STREAM) block_sum_put<kRow>(lds, pos, tri6(i, j), v);
                 else acc[tri6(i, j)] = FIRST ? v : acc[tri6(i, j)] + v;
             }
         }
         if (mine(21 + i)) {
             const double gi = __builtin_fma(J[0][i], r[0], J[1][i] * r[1]);
-            if constexpr (STREAM) block_sum_put(lds, pos, 21 + i, gi);
+            if constexpr (STREAM) block_sum_put<kRow>(lds, pos, 21 + i, gi);
             else acc[21 + i] = FIRST ? gi : acc[21 + i] + gi;
         }
     }
     if (mine(27)) {
         const double ss = __builtin_fma(r[0], r[0], r[1] * r[1]);
-        if constexpr (STREAM) block_sum_put(lds, pos, 27, ss);
+        if constexpr (STREAM) block_sum_put<kRow>(lds, pos, 27, ss);
         else acc[27] = FIRST ? ss : acc[27] + ss;
     }
 }
