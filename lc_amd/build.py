@@ -6,6 +6,7 @@
     posecov  lc_amd/_C/liblc_amd_posecov.so  lc_amd/csrc/posecov/     include/lc_amd_posecov.h  the test-time pose covariance
     render   lc_amd/_C/liblc_amd_render.so   lc_amd/csrc/render/      include/lc_amd_render.h   the depth rasteriser
     crop     lc_amd/_C/liblc_amd_crop.so     lc_amd/csrc/crop/        include/lc_amd_crop.h     the zoom-in crops
+    models   lc_amd/_C/liblc_amd_models.so   lc_amd/csrc/models/      include/lc_amd_models.h   model preparation (an offline tool's kernels)
 
 A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`).
 Every function takes the library it works on as a `Target` (default: the hot-path library)."""
@@ -58,13 +59,21 @@ OPTIM = _side("optim")
 POSECOV = _side("posecov", (SHARED_H,))
 RENDER = _side("render")
 CROP = _side("crop")
+MODELS = _side("models", (SHARED_H,))  # the offline model preparation (lc_amd.models, python -m lc_amd.prep_models)
 _ALL = (MAIN, OPTIM, POSECOV, RENDER, CROP)
+_TOOLS = (MODELS,)
 HASH_MARKER = MAIN.hash_marker
 
 
 def all_targets():
-    """Every library of the package, in build order."""
+    """Every library of the training and test-time paths, in build order."""
     return _ALL
+
+
+def tool_targets():
+    """The libraries behind the offline tools: built along with all_targets() by `python __graft_entry__.py build`, loaded by no training
+    or test-time path."""
+    return _TOOLS
 
 
 def sources(target: Target = MAIN):
@@ -218,5 +227,5 @@ def build_variant(name: str, flags, verbose: bool = False) -> str:
 
 
 if __name__ == "__main__":
-    for t in all_targets():
+    for t in all_targets() + tool_targets():
         print(build(force=True, verbose=True, target=t))
