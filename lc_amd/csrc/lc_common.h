@@ -54,9 +54,13 @@ __device__ __forceinline__ void wave_sync() {
 // Sum of K doubles per lane over the 64 lanes of a ONE-wavefront workgroup, result in every lane, through LDS.
 // Lane t stores v[k] at lds[k*68 + t + 2*(t/32)] (32-double segments padded by 16 bytes, rows of 68 doubles: conflict-free
 // ds_write_b64 and ds_read_b128); lane r < 2 K sums one segment with eight + eight 16-byte reads, the two partial sums of a row meet
-// by DPP, the K totals are re-read by all lanes.  Measured cheaper than the permlane/DPP reduce-scatter + broadcast for a lone wave
-// (each 64-bit cross-lane exchange costs 25-32 cycles, scripts/ubench/fp64_latency.cpp).  Needs K <= 32 and K*68 + K doubles of LDS.
-// (Four-wave workgroups sum in registers: block_sum_waves4 below.)
+// by DPP, the K totals are re-read by all lanes.  Measured cheaper than the permlane/DPP reduce-scatter + broadcast for a lone wave WITH
+// ALL 28 ENTRIES (a reduce-scatter of 32: 30 exchanges; a dependent 64-bit cross-lane exchange costs 25-32 cycles,
+// scripts/ubench/fp64_latency.cpp).  That measurement does not carry over to the 14 entries a wave of the two-wave team owns: there the
+// register tree (16 exchanges of 7 instructions or fewer, block_sum_team2_reg below) is the faster form -- the sum itself is ~100 cycles
+// longer than through LDS, the per-point phase ~230 cycles shorter without its 14 stores (profiles/teamreg/NOTES.md).  The one-wave form
+// with 14 + 14 entries in registers has not been measured.  Needs K <= 32 and K*68 + K doubles of LDS.
+// (Four-wave workgroups sum in registers too: block_sum_waves4 below.)
 // The sum is called in two halves: block_sum_open() (the previous totals have been read), then the caller stores its K values itself
 // with block_sum_put() AS IT PRODUCES THEM -- the LDS stores of a lone wave drain at about 40 B/clk (MI355X_MICROARCH.md, LDS: one wave
 // gets half the store rate), 360 cycles for 28 doubles x 64 lanes, and issued early they drain behind the arithmetic that produces
@@ -151,6 +155,7 @@ __device__ __forceinline__ void arrival_reset(unsigned* words, int tid) {
     if (tid <= kArrivalShards) xcd_store(words + tid * kArrivalStride, 0u);
 }
 
+// (The LDS form of the team's sum: built with -DLC_PNP_TEAM_REGSUM=0; the shipped form is block_sum_team2_reg below.)
 // The one-wave sum played by a TEAM of two wavefronts that both hold all 64 values of every entry (lane = point in both:
 // the pose unit's latency build, where half the SIMDs idle next to a wave that is bound by instruction issue).  Wave W produces and
 // stores only the entries k with k % 2 == W -- block_sum_put<kTeamRowDoubles>, the slots of the one-wave form in rows of the team's own
@@ -185,6 +190,27 @@ __device__ __forceinline__ void block_sum_team2(double (&v)[K], double* lds, int
     double* tot = lds + K * kTeamRowDoubles + K * phase;
     phase ^= 1;
     if (lane < 2 * K && (lane % 4) == 0) tot[entry] = s;  // the lane whose adds were x + y, then segment 0 + segment 1
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = tot[k];
+}
+
+// block_sum_team2 without the slots: wave W reduce-scatters its K / 2 entries (v[k], k % 2 == W, formed in registers) with the exchange
+// tree that pairs the lanes as block_sum_segment pairs lane t's slot t (shared/lc_shared.h: wave_reduce_scatter_lds_order), so every
+// total has the LDS forms' bits; one lane per entry stores it into the two-phase rows of totals, which are all the LDS this form needs.
+// The barrier, the rows' alternation and the K reads are block_sum_team2's.  lds: sum_team2_reg_lds_doubles(K) doubles.
+constexpr int sum_team2_reg_lds_doubles(int K) { return 2 * K; }
+template <int K, int W>
+__device__ __forceinline__ void block_sum_team2_reg(double (&v)[K], double* lds, int lane, int& phase) {
+    static_assert(K % 2 == 0 && K <= 32 && (W == 0 || W == 1), "an even number of entries dealt to two waves");
+    double w[K / 2];
+#pragma unroll
+    for (int i = 0; i < K / 2; ++i) w[i] = v[2 * i + W];
+    const double s = wave_reduce_scatter_lds_order<K / 2>(w, lane);
+    double* tot = lds + K * phase;
+    phase ^= 1;
+    const int entry = reduce_scatter_lds_order_entry<K / 2>((lane >> 1) & 15);
+    if (lane < 32 && (lane & 1) == 0 && entry >= 0) tot[2 * entry + W] = s;
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < K; ++k) v[k] = tot[k];

@@ -51,13 +51,20 @@
 #ifndef LC_PNP_TEAM2
 #define LC_PNP_TEAM2 1  // A/B switch: the latency builds of the one-correspondence-per-lane solve (plain instantiations: lc_pnp_latency.hip, lc_fused_kernel.h) run TWO wavefronts per pose that share the products and the block sum (TeamWave below); 0 = one wavefront per pose
 #endif
+#ifndef LC_PNP_TEAM_REGSUM
+#define LC_PNP_TEAM_REGSUM 1  // A/B switch: the team sums each wave's 14 entries in registers (lc_common.h: block_sum_team2_reg); 0 = through their LDS slots (block_sum_team2)
+#endif
 
 namespace lc {
 namespace pnp {
 
 template <int NW>
 constexpr int kPnpLdsDoubles = [] { static_assert(NW == 1, "the four-wave kernels: kPnpWideReservedLdsDoubles"); return block_sum_lds_doubles(28); }();  // block_sum_close<28>
+#if LC_PNP_TEAM_REGSUM
+constexpr int kPnpTeamLdsDoubles = sum_team2_reg_lds_doubles(28);  // block_sum_team2_reg<28>: the two rows of totals
+#else
 constexpr int kPnpTeamLdsDoubles = sum_team2_lds_doubles(28);  // block_sum_team2<28>: the one-wave slots in rows of kTeamRowDoubles and a second row of totals
+#endif
 // Static LDS of the four-wave kernels: 7 644 doubles (61 KB) are RESERVED -- the size of a slot per thread and entry -- where
 // block_sum_waves4 touches 192 doubles (block_sum_split: 194, in the split kernels' own array).  The size is in the kernel descriptor
 // and decides how many workgroups share a compute unit, so shrinking it changes the speed and wants a measurement: kept to the byte
@@ -106,7 +113,8 @@ __device__ __forceinline__ void make_rot(const double aa[3], Rot& o) {
 // (columns of J pre-multiplied by the Jacobi scaling sc: acc holds Js^T Js and Js^T r directly)
 // FIRST: acc is written (not added to) -- saves zero-filling 32 accumulators and one add per entry when a lane owns one point.
 // STREAM: (FIRST only) every finished entry goes straight to its LDS slot of the block sum instead of into acc[]
-// PAR (STREAM only): 0 / 1 = only the entries of that parity are formed and stored (the two waves of a team, block_sum_team2); -1 = all
+// PAR (FIRST only): 0 / 1 = only the entries of that parity are formed (the two waves of a team: stored with STREAM, block_sum_team2; left
+// in acc[] without, block_sum_team2_reg; the other parity's acc[] stays unwritten); -1 = all
 template <bool FIRST, bool STREAM = false, int PAR = -1>
 __device__ __forceinline__ void accumulate_point(const Point& pt, const Rot& rt, const double t[3], const double k[6],
                                                  const double (&sc)[6], double (&acc)[28], double* lds = nullptr, int pos = 0) {
@@ -141,7 +149,7 @@ __device__ __forceinline__ void accumulate_point(const Point& pt, const Rot& rt,
 #pragma unroll
         for (int m = 0; m < 3; ++m) J[rr][3 + m] *= sc[3 + m];
     }
-    static_assert(PAR < 0 || STREAM, "entries are dealt by parity where they go to their LDS slots");
+    static_assert(PAR < 0 || FIRST, "entries are dealt by parity where a lane owns one point");
     constexpr auto mine = [](int k) { return PAR < 0 || (k & 1) == PAR; };  // (folds once the loops are unrolled)
     constexpr int kRow = PAR < 0 ? 68 : kTeamRowDoubles;                    // the team's LDS rows have their own stride (block_sum_team2)
 #pragma unroll
@@ -273,7 +281,8 @@ __device__ __forceinline__ double norm6(const double (&v)[6]) {
 // forms differ in where a thread's correspondences live and in how the 28 sums of an evaluation are formed:
 //   1. ONE wave (N <= 64, the metric's shape), one correspondence per lane, in registers across the whole solve (REG).  The 28 entries
 //      are streamed to their LDS slots as they are formed, then block_sum_close<28>.  bc: kPnpLdsDoubles<1>.
-//   2. The two-wave TEAM: form 1 played by the two wavefronts of a 128-thread workgroup (TeamWave below), block_sum_team2.
+//   2. The two-wave TEAM: form 1 played by the two wavefronts of a 128-thread workgroup (TeamWave below), each with its 14 entries in
+//      registers, block_sum_team2_reg (-DLC_PNP_TEAM_REGSUM=0: streamed to LDS slots, block_sum_team2).
 //   3. FOUR waves (N <= 256), one correspondence per thread in registers (REG): accumulate_point<true>, then block_sum_waves4.
 //   4. FOUR waves over rows of any width (e.g. the dense heads' N = 1024..1849, where four waves cut the per-evaluation point loop by
 //      four): each thread adds up its correspondences -- cached prefix, tail, rescue or plain loop, below -- then block_sum_waves4,
@@ -295,8 +304,8 @@ __device__ __forceinline__ double norm6(const double (&v)[6]) {
 //   TEAM = 0 / 1 (TeamWave; -1 = off): wave TEAM of a 128-thread workgroup whose TWO wavefronts solve ONE pose (`lane` = lane of the
 //   wave, bc: kPnpTeamLdsDoubles).  Both waves hold all correspondences and run the whole solve -- load, quaternion -> angle-axis,
 //   make_rot, geometry and Jacobian rows, Jacobi scaling, LDL^T, the schedule: the same expressions on the same values, so they take
-//   every branch together -- but each forms, stores and sums only the 14 of the 28 entries J^T J | J^T r | r^T r of its parity
-//   (lc_common.h: block_sum_team2, one workgroup barrier per evaluation; every break / continue / return is taken by both waves, so
+//   every branch together -- but each forms and sums only the 14 of the 28 entries J^T J | J^T r | r^T r of its parity
+//   (lc_common.h: block_sum_team2_reg, one workgroup barrier per evaluation; every break / continue / return is taken by both waves, so
 //   their barrier counts agree; the n < 3 exit comes before the first).  Every total is summed in the one-wave form's order: the same
 //   bits.  Wave 0 stores (the caller passes store = false to wave 1).
 struct FormDefaults {
@@ -436,11 +445,18 @@ __device__ __forceinline__ void solve_pose(const PnpParams& p, int b, int lane, 
             LC_PSTAMP(3);
             block_sum_close<28>(acc, bc, lane);
         } else if constexpr (NW == 1) {
+#if LC_PNP_TEAM_REGSUM
+            // form 2.  This wave's half of the 28 partial sums stays in registers and is summed there; the sibling wave forms the other half
+            accumulate_point<true, false, TEAM>(rp, rt, t, cam, sc, acc);
+            LC_PSTAMP(3);
+            block_sum_team2_reg<28, TEAM>(acc, bc, lane, sum_phase);
+#else
             // form 2.  This wave's half of the 28 partial sums goes to LDS as it is produced; the sibling wave forms the other half
             const int pos = block_sum_open(lane);
             accumulate_point<true, true, TEAM>(rp, rt, t, cam, sc, acc, bc, pos);
             LC_PSTAMP(3);
             block_sum_team2<28, TEAM>(acc, bc, lane, sum_phase);
+#endif
         } else if constexpr (REG) {
             // form 3.  The register block sum here too: 12.4 -> 11.6 us at 64 x 256 against sums streamed through LDS
             accumulate_point<true>(rp, rt, t, cam, sc, acc);

@@ -102,6 +102,67 @@ __device__ __forceinline__ int scatter16_base(int lane, int R) {
     return R * (((lane >> 5) & 1) * 8 + ((lane >> 4) & 1) * 4 + ((lane >> 3) & 1) * 2 + ((lane >> 2) & 1));
 }
 
+// Reduce-scatter of K <= 16 doubles across a wave that pairs the lanes as the LDS block sum pairs its slots (lc_common.h:
+// block_sum_segment over lane t's slot t, then segment 0 + segment 1): lane xor 16, 8, 4, 2, 1, 32, in that order.  Every add is
+// own + partner of the two partial sums the LDS tree adds at that level, and fp64 addition is commutative: the totals have that tree's bits
+// (wave_reduce_scatter16 pairs 32, 16, mirror-15, mirror-7, 2, 1: other partial sums, other roundings).
+// The values halve at every stage: the 16-lane exchange is v_permlane16_swap, the 8- and 4-lane exchanges are DPP row moves under bank
+// masks (the lanes that keep the upper half are whole banks of 4), the 2-lane exchange needs a per-lane select; the last two stages move
+// one value.  With K = 14 entry e travels in slot e + e / 7 of the 16, so that the two slots nobody owns are
+// 7 and 15: partners at the first stage (no exchange at all), and the upper half of one pair at the second (a plain own + partner).
+// Returns, in lane l, the total of the entry in slot (l >> 1) & 15 (reduce_scatter_lds_order_entry; -1: nobody's slot, any finite or
+// non-finite value); lanes l, l ^ 1 and l ^ 32 hold the same total.
+template <int K>
+__device__ __forceinline__ constexpr int reduce_scatter_lds_order_entry(int slot) {
+    static_assert(K == 14 || K == 16, "16 slots, or 14 with slots 7 and 15 empty");
+    if (K == 16) return slot;
+    return (slot & 7) == 7 ? -1 : slot - (slot >> 3);
+}
+constexpr int kDppRowRor8 = 0x128;  // row_ror:8: lane i <- lane i ^ 8 of its row of 16
+constexpr int kDppRowShl4 = 0x104;  // row_shl:4: lane i <- lane i + 4 of its row
+constexpr int kDppRowShr4 = 0x114;  // row_shr:4: lane i <- lane i - 4 of its row
+template <int K>
+__device__ __forceinline__ double wave_reduce_scatter_lds_order(const double (&v)[K], int lane) {
+    constexpr auto entry = reduce_scatter_lds_order_entry<K>;
+    static_assert((entry(7) < 0) == (entry(15) < 0), "an empty slot's partner is empty");
+    double w[8];
+    // xor 16: lanes with bit 4 clear go on with slots 0-7, the others with slots 8-15
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        if (entry(i) >= 0) w[i] = swap16_add(v[entry(i)], v[entry(i + 8)]);
+    }
+    // xor 8: bit 3 clear (banks 0-1 of the row) keeps lo, set (banks 2-3) keeps hi.  The kept half by a select, the received one by two
+    // moves onto the same register (7 instructions an exchange; the select as a third masked move costs two copies more).  Written out
+    // with constant indices: in a loop the compiler turns the select of w[i] and w[i + 4] into a load at a selected index -- scratch
+    const bool up8 = (lane & 8) != 0, up4 = (lane & 4) != 0;
+    auto exchange8 = [up8](double lo, double hi) {
+        const double keep = up8 ? hi : lo;
+        double recv = dpp_mov_f64<kDppRowRor8>(lo, lo);       // every lane <- partner's lo ...
+        recv = dpp_mov_f64<kDppRowRor8, 0xC>(recv, hi);       // ... the upper lanes <- partner's hi instead
+        return keep + recv;
+    };
+    w[0] = exchange8(w[0], w[4]);
+    w[1] = exchange8(w[1], w[5]);
+    w[2] = exchange8(w[2], w[6]);
+    if constexpr (entry(7) >= 0) w[3] = exchange8(w[3], w[7]);
+    else w[3] += dpp_mov_f64<kDppRowRor8>(w[3], w[3]);        // nobody's slot above: the lanes with bit 3 set end with a copy
+    // xor 4: bit 2 clear (banks 0 and 2) keeps lo, set (banks 1 and 3) keeps hi; the partner is 4 lanes up / down
+    auto exchange4 = [up4](double lo, double hi) {
+        const double keep = up4 ? hi : lo;
+        double recv = dpp_mov_f64<kDppRowShl4, 0x5>(lo, lo);  // the lower lanes <- lo of the lane 4 up ...
+        recv = dpp_mov_f64<kDppRowShr4, 0xA>(recv, hi);       // ... the upper lanes <- hi of the lane 4 down
+        return keep + recv;
+    };
+    w[0] = exchange4(w[0], w[2]);
+    w[1] = exchange4(w[1], w[3]);
+    // xor 2: bit 1 clear keeps w[0], set keeps w[1] (half a bank: a select per lane)
+    const bool up = (lane & 2) != 0;
+    const double keep = up ? w[1] : w[0], send = up ? w[0] : w[1];
+    double s = keep + dpp_mov_f64<kDppQuadXor2>(send, send);
+    s += dpp_mov_f64<kDppQuadXor1>(s, s);  // xor 1
+    return swap32_add(s, s);               // xor 32
+}
+
 // index of (i,j), i<=j, in a packed upper-triangular 6x6 (21 entries, row-major)
 __host__ __device__ constexpr int tri6(int i, int j) { return i * 6 - (i * (i - 1)) / 2 + (j - i); }
 
