@@ -43,6 +43,23 @@ __device__ __forceinline__ float torch_lerp(float a, float b, float w) {
     return w < 0.5f ? a + w * (b - a) : b - (b - a) * (1.f - w);
 }
 
+__device__ __forceinline__ int wave_sum(int x) {  // sum / minimum over the wavefront, the same value in every lane
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, kWave);
+    return x;
+}
+__device__ __forceinline__ unsigned wave_min(unsigned x) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x = min(x, (unsigned)__shfl_xor((int)x, m, kWave));
+    return x;
+}
+
+// test.py:94-106's three modes (0 mask, 1 quantile, 2 quantile_in_mask): the weight the threshold is searched over and compared with -- mode 2:
+// (inv_std * seg).sum(-1), a hidden entry weighs 0 -- and which entries are kept (s: the two inv_std, g: the mask bit).  By reference: read only
+// where the mode needs them, as written out at the call sites before (by value, lc_dense_select_kernel waited for the mask byte amid its first loads)
+template <class G> __device__ __forceinline__ float select_weight(int mode, const float2& s, const G& g) { return (mode == 2 && !g) ? 0.f : s.x + s.y; }
+template <class G> __device__ __forceinline__ bool select_keeps(int mode, float w, const G& g, float thr) { return mode == 0 ? g != 0 : (w >= thr && (mode == 1 || g != 0)); }
+
 // One count into an LDS histogram per lane that is `active`.  Weights cluster -- a quantile inside a mask zeroes every weight outside
 // it, and the top byte of positive floats of similar size is the same -- so a plain atomicAdd per lane sends hundreds of adds to ONE
 // address, which the LDS serialises.  Two rounds of leader aggregation (the lanes that share the first active lane's bin are counted
@@ -74,6 +91,9 @@ struct Entry {
     int src;
     unsigned char g;
 };
+
+__device__ __forceinline__ RowCopy select_rows(const SelectParams& p) { return RowCopy{nullptr, nullptr, nullptr, nullptr, p.o_pts2d, p.o_w, p.o_pts3d, p.o_index, p.square}; }  // the outputs as a row writer (lc_select_rows.h; no source arrays: entries come out of registers)
+__device__ __forceinline__ void put(const RowCopy& rows, size_t base, int o, const Entry& e) { rows.entry_from(base, o, e.u.x, e.u.y, e.s, e.X[0], e.X[1], e.X[2], e.src); }
 
 // Rows held in arrays (lc_dense_select_f32)
 struct ArraySource {
@@ -123,15 +143,86 @@ struct MapSource {
     __device__ __forceinline__ Entry finish(Entry e, float v) const {
         e.s = make_float2(__expf(e.s.x - lse) * scale, __expf(e.s.y - lse) * scale);
         for (int d = 0; d < 3; ++d) e.X[d] *= ns[d];
-        e.g = vis ? ((1.f / (1.f + expf(-v))) > vis_thresh ? 1 : 0) : 0;  // torch.sigmoid's own formula
+        e.g = vis ? (visible(v) ? 1 : 0) : 0;
         return e;
     }
+    __device__ __forceinline__ bool visible(float v) const { return (1.f / (1.f + expf(-v))) > vis_thresh; }  // the mask bit of visibility logit v (test.py:88-90) by torch.sigmoid's own formula, where there is a map (`vis`: the callers' test)
     __device__ __forceinline__ Entry load(int n) const {
         float v;
         const Entry e = fetch(n, v);
         return finish(e, v);
     }
 };
+
+// Object b of the front end's arguments as a MapSource; its log-sum-exp (lse = 0 here) is the caller's to form
+template <typename T, typename TX>
+__device__ __forceinline__ MapSource<T, TX> make_map_source(const DenseParams& d, int b) {
+    MapSource<T, TX> src;
+    src.lg = static_cast<const T*>(d.wlogits) + (size_t)b * d.wl_bs;
+    src.xyz = d.xyz ? static_cast<const TX*>(d.xyz) + (size_t)b * d.xyz_bs : nullptr;
+    src.vis = d.vis_logits ? static_cast<const T*>(d.vis_logits) + (size_t)b * d.vis_bs : nullptr;
+    src.vis_thresh = d.vis_thresh;
+    src.HW = d.H * d.W; src.W = d.W; src.top = d.top; src.left = d.left; src.sample = d.sample;
+    src.Wn = (d.W - d.left + d.sample - 1) / d.sample;
+    src.lse = 0.f;
+    src.scale = map_scalar_at(d.wscale, d.wscale_dtype, b);
+    for (int k = 0; k < 3; ++k) src.ns[k] = d.noc_scale ? d.noc_scale[3 * b + k] : 1.f;
+    return src;
+}
+
+__device__ __forceinline__ unsigned weight_key(float w) {
+    const unsigned u = __float_as_uint(w);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // ascending unsigned order == ascending float order
+}
+__device__ __forceinline__ float key_weight(unsigned key) { return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key); }  // its inverse
+
+// q -> the rank q (n - 1) torch.quantile interpolates at and the two order statistics around it; seg_total: the row's visible entries (mode 2)
+struct QuantileRank { float rank, lo; int klo, khi; };
+__device__ __forceinline__ QuantileRank quantile_rank(const SelectParams& p, int n, int seg_total) {
+    float q = p.quantile;
+    if (p.mode == 2) q = 1.f - p.one_minus_q * ((float)seg_total / (float)n);  // test.py:102-103, fp32 like the tensor op
+    q = fminf(fmaxf(q, 0.f), 1.f);
+    const float rank = q * (float)(n - 1), lo = floorf(rank), hi = ceilf(rank);
+    return QuantileRank{rank, lo, (int)lo, min((int)hi, n - 1)};
+}
+__device__ __forceinline__ float quantile_value(unsigned found0, unsigned found1, const QuantileRank& qr) {  // the threshold from the keys at ranks klo, khi: the same two floats in every thread
+    const float vlo = key_weight(found0), vhi = qr.khi != qr.klo ? key_weight(found1) : vlo;
+    return torch_lerp(vlo, vhi, qr.rank - qr.lo);
+}
+
+// One radix pass' scan of its 256 bins (LDS, behind the caller's barrier) by the calling wavefront, the same result in every lane: lane l owns bins
+// 4l .. 4l+3, exclusive prefix over the lanes, then the bin holding rank k (0-based among the keys counted) and the rank within it.  last (the lowest
+// digit: the bins are exact keys): also how many copies of the found key there are, and the next key present under the same 24-bit prefix (256: none).
+struct RadixPick { int bin, rest, in_bin, next_bin; };
+template <bool CAN_BE_LAST>  // false: the caller never asks (quantile_threshold counts instead); as a run-time `false` the dead half cost the wide kernel 4.7 us
+__device__ __forceinline__ RadixPick radix_pick(const int* bins, int lane, int k, bool last = CAN_BE_LAST) {
+    const int c0 = bins[4 * lane], c1 = bins[4 * lane + 1], c2 = bins[4 * lane + 2], c3 = bins[4 * lane + 3];
+    const int mine = c0 + c1 + c2 + c3;
+    int incl = mine;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const int up = __shfl_up(incl, d, kWave);
+        if (lane >= d) incl += up;
+    }
+    const int excl = incl - mine;
+    const bool hit = k >= excl && k < incl;  // exactly one lane
+    int r = k - excl, bin = 4 * lane, cb = c0;
+    if (r >= c0) { r -= c0; ++bin; cb = c1; if (r >= c1) { r -= c1; ++bin; cb = c2; if (r >= c2) { r -= c2; ++bin; cb = c3; } } }
+    const int owner = __ffsll((long long)__ballot(hit)) - 1;
+    RadixPick pk{__shfl(bin, owner, kWave), __shfl(r, owner, kWave), 0, 256};
+    if (CAN_BE_LAST && last) {
+        pk.in_bin = __shfl(cb, owner, kWave);
+        int nb = 256;
+        if (4 * lane + 3 > pk.bin) {
+            if (c3 > 0 && 4 * lane + 3 > pk.bin) nb = 4 * lane + 3;
+            if (c2 > 0 && 4 * lane + 2 > pk.bin) nb = 4 * lane + 2;
+            if (c1 > 0 && 4 * lane + 1 > pk.bin) nb = 4 * lane + 1;
+            if (c0 > 0 && 4 * lane > pk.bin) nb = 4 * lane;
+        }
+        pk.next_bin = (int)wave_min((unsigned)nb);
+    }
+    return pk;
+}
 
 // torch.quantile's threshold of the row whose n order-preserving integer keys the calling workgroup (kThreads threads) has just written to
 // `keys` (LDS; no barrier yet); segc: this thread's count of visible entries (mode 2).  Same value in every thread.
@@ -141,11 +232,6 @@ struct MapSource {
 // are unchanged bit for bit.  Barriers are what this costs (16 wavefronts each): every pass has ONE -- the histogram of pass k is scanned
 // by every wavefront for itself (no broadcast), the histogram of pass k+1 was zeroed while pass k was counting, and with three of them in
 // rotation the one zeroed during pass k+2 is the one whose scan ended before pass k+1's barrier.
-__device__ __forceinline__ unsigned weight_key(float w) {
-    const unsigned u = __float_as_uint(w);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // ascending unsigned order == ascending float order
-}
-__device__ __forceinline__ float key_weight(unsigned key) { return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key); }  // its inverse
 // key_at(j, i): key of entry i = tid + j * kThreads (from LDS, or from the caller's registers: then ITERS = the number of entries a thread
 // holds, and the walks over them are unrolled so that j is a compile-time register index)
 template <int ITERS = 0, class KeyAt>
@@ -157,28 +243,22 @@ __device__ __forceinline__ float quantile_threshold(const SelectParams& p, int n
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid < 256) hist[0][tid] = 0;
     if (p.mode == 2) {
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) segc += __shfl_xor(segc, m, kWave);
+        segc = wave_sum(segc);
         if (lane == 0) wave_seg[wave] = segc;
     }
     __syncthreads();
-    float q = p.quantile;
+    int seg_total = 0;
     if (p.mode == 2) {
-        int seg_total = 0;
 #pragma unroll
         for (int w = 0; w < kWaves; ++w) seg_total += wave_seg[w];
-        q = 1.f - p.one_minus_q * ((float)seg_total / (float)n);  // test.py:102-103, fp32 like the tensor op
     }
-    q = fminf(fmaxf(q, 0.f), 1.f);
-    const float rank = q * (float)(n - 1);
-    const float lo = floorf(rank), hi = ceilf(rank);
-    const int klo = (int)lo, khi = min((int)hi, n - 1);
+    const QuantileRank qr = quantile_rank(p, n, seg_total);
     // rank klo by the radix select; rank khi = klo + 1 is then either the same key (a duplicate: more than klo + 1 keys are <= it)
     // or the smallest key above it -- one counting / min pass instead of four more histogram passes
     unsigned found[2] = {0u, 0u};
     {
         unsigned prefix = 0u, mask = 0u;
-        int k = klo;  // 0-based rank among the elements that still match the prefix
+        int k = qr.klo;  // 0-based rank among the elements that still match the prefix
         for (int pass = 3; pass >= 0; --pass) {
             const int shift = 8 * pass, cur = (3 - pass) % 3, nxt = (cur + 1) % 3;
             if (tid < 256) hist[nxt][tid] = 0;
@@ -198,27 +278,14 @@ __device__ __forceinline__ float quantile_threshold(const SelectParams& p, int n
                 }
             }
             __syncthreads();
-            // every wavefront: lane l owns bins 4l .. 4l+3, exclusive prefix over the lanes, then the bin holding rank k
-            const int c0 = hist[cur][4 * lane], c1 = hist[cur][4 * lane + 1], c2 = hist[cur][4 * lane + 2], c3 = hist[cur][4 * lane + 3];
-            const int mine = c0 + c1 + c2 + c3;
-            int incl = mine;
-#pragma unroll
-            for (int d = 1; d < kWave; d <<= 1) {
-                const int up = __shfl_up(incl, d, kWave);
-                if (lane >= d) incl += up;
-            }
-            const int excl = incl - mine;
-            const bool hit = k >= excl && k < incl;  // exactly one lane
-            int r = k - excl, bin = 4 * lane;
-            if (r >= c0) { r -= c0; ++bin; if (r >= c1) { r -= c1; ++bin; if (r >= c2) { r -= c2; ++bin; } } }
-            const int owner = __ffsll((long long)__ballot(hit)) - 1;
-            prefix |= (unsigned)__shfl(bin, owner, kWave) << shift;
+            const RadixPick pk = radix_pick<false>(hist[cur], lane, k);  // every wavefront for itself
+            prefix |= (unsigned)pk.bin << shift;
             mask |= 255u << shift;
-            k = __shfl(r, owner, kWave);
+            k = pk.rest;
         }
         found[0] = found[1] = prefix;
     }
-    if (khi != klo) {  // uniform
+    if (qr.khi != qr.klo) {  // uniform
         int le = 0;
         unsigned above = 0xFFFFFFFFu;
         auto count = [&](int j, int i) {
@@ -233,21 +300,17 @@ __device__ __forceinline__ float quantile_threshold(const SelectParams& p, int n
         } else {
             for (int i = tid, j = 0; i < n; i += kThreads, ++j) count(j, i);
         }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            le += __shfl_xor(le, m, kWave);
-            above = min(above, (unsigned)__shfl_xor((int)above, m, kWave));
-        }
+        le = wave_sum(le);
+        above = wave_min(above);
         if (lane == 0) { wave_le[wave] = le; wave_above[wave] = above; }
         __syncthreads();
         int le_total = 0;
         unsigned above_min = 0xFFFFFFFFu;
 #pragma unroll
         for (int w = 0; w < kWaves; ++w) { le_total += wave_le[w]; above_min = min(above_min, wave_above[w]); }
-        if (le_total <= khi) found[1] = above_min;  // no duplicate reaches rank khi: the next distinct key
+        if (le_total <= qr.khi) found[1] = above_min;  // no duplicate reaches rank khi: the next distinct key
     }
-    const float vlo = key_weight(found[0]), vhi = khi != klo ? key_weight(found[1]) : vlo;
-    return torch_lerp(vlo, vhi, rank - lo);  // every thread forms it from the same two floats
+    return quantile_value(found[0], found[1], qr);
 }
 
 // Order-preserving compaction of a row, 1024 candidates (one per thread) at a time: slot(keep, more) returns where this thread's entry
@@ -283,7 +346,7 @@ template <class Source>
 __device__ __forceinline__ void select_row(const SelectParams& p, int b, int n, const Source& src, const Entry (&ec)[kCache], float* srt) {
     const int tid = threadIdx.x;
     const size_t base = (size_t)b * p.N;
-    auto weight_of = [&](const Entry& e) { return (p.mode == 2 && !e.g) ? 0.f : e.s.x + e.s.y; };  // mode 2: (inv_std * seg).sum(-1)
+    auto weight_of = [&](const Entry& e) { return select_weight(p.mode, e.s, e.g); };
     float thr = -FLT_MAX;
     if (p.mode != 0 && n > 0) {
         unsigned* keys = reinterpret_cast<unsigned*>(srt);
@@ -298,17 +361,12 @@ __device__ __forceinline__ void select_row(const SelectParams& p, int b, int n, 
         for (int i = tid + kCache * kThreads; i < n; i += kThreads) stage(src.load(i), i);
         thr = quantile_threshold(p, n, [&](int, int i) { return keys[i]; }, segc);
     }
-    const RowCopy rows{nullptr, nullptr, nullptr, nullptr, p.o_pts2d, p.o_w, p.o_pts3d, p.o_index, p.square};
-    auto put = [&](const Entry& e, int o) { rows.entry_from(base, o, e.u.x, e.u.y, e.s, e.X[0], e.X[1], e.X[2], e.src); };
+    const RowCopy rows = select_rows(p);
     Compactor cmp;
     auto chunk = [&](int i0, const Entry& e, bool mine) {  // mine: this thread has an entry in the chunk (e)
-        bool keep = false;
-        if (mine) {
-            if (p.mode == 0) keep = e.g != 0;
-            else keep = weight_of(e) >= thr && (p.mode == 1 || e.g != 0);
-        }
+        const bool keep = mine && select_keeps(p.mode, weight_of(e), e.g, thr);
         const int o = cmp.slot(keep, i0 + kThreads < n);
-        if (keep) put(e, o);
+        if (keep) put(rows, base, o, e);
     };
 #pragma unroll
     for (int k = 0; k < kCache; ++k) {
@@ -319,7 +377,7 @@ __device__ __forceinline__ void select_row(const SelectParams& p, int b, int n, 
         const bool mine = i0 + tid < n;
         chunk(i0, mine ? src.load(i0 + tid) : ec[0], mine);
     }
-    const int total = pad_rows(p.pose0 + b, n, cmp.running, p.min_count, p.seed, [&](int i, int k) { put(src.load(i), k); });  // test.py:108-113
+    const int total = pad_rows(p.pose0 + b, n, cmp.running, p.min_count, p.seed, [&](int i, int k) { put(rows, base, k, src.load(i)); });  // test.py:108-113
     if (tid == 0) p.counts[b] = total;
 }
 
@@ -369,9 +427,9 @@ __device__ __forceinline__ void select_row_wide(const SelectParams& p, int b, Ma
 #pragma unroll
     for (int k = 0; k < kWideCache; ++k) {
         w[k] = make_float2(__expf(w[k].x - src.lse) * src.scale, __expf(w[k].y - src.lse) * src.scale);
-        if (src.vis && (1.f / (1.f + expf(-vraw[k]))) > src.vis_thresh) gbits |= 1u << k;  // torch.sigmoid's own formula
+        if (src.vis && src.visible(vraw[k])) gbits |= 1u << k;
     }
-    auto weight_of = [&](int k) { return (p.mode == 2 && !((gbits >> k) & 1u)) ? 0.f : w[k].x + w[k].y; };
+    auto weight_of = [&](int k) { return select_weight(p.mode, w[k], (gbits >> k) & 1u); };
     float thr = -FLT_MAX;
     if (p.mode != 0) {
         // the keys never leave the registers: a thread's entry j of every pass is its own w[j] (the generic path stages them in LDS)
@@ -385,7 +443,7 @@ __device__ __forceinline__ void select_row_wide(const SelectParams& p, int b, Ma
 #endif
     }
     LC_FS_STAMP(3);
-    const RowCopy rows{nullptr, nullptr, nullptr, nullptr, p.o_pts2d, p.o_w, p.o_pts3d, p.o_index, p.square};
+    const RowCopy rows = select_rows(p);
     // Order-preserving compaction of all 16 chunks of 1024 candidates with THREE barriers (one barrier pair per chunk was 32 of them,
     // 16 wavefronts each): the keep flags of a thread's 16 entries are known at once, so every wavefront posts its 16 per-chunk counts,
     // the first 256 threads scan the 16 x 16 table in (chunk, wavefront) order, and a thread's entry k goes to
@@ -397,11 +455,7 @@ __device__ __forceinline__ void select_row_wide(const SelectParams& p, int b, Ma
 #pragma unroll
     for (int k = 0; k < kWideCache; ++k) {
         const int i = tid + k * kThreads;
-        bool keep = false;
-        if (i < n) {
-            const bool g = (gbits >> k) & 1u;
-            keep = p.mode == 0 ? g : (weight_of(k) >= thr && (p.mode == 1 || g));
-        }
+        const bool keep = i < n && select_keeps(p.mode, weight_of(k), (gbits >> k) & 1u, thr);
         const unsigned long long bal = __ballot(keep);
         if (keep) keepbits |= 1u << k;
         before[k >> 2] |= (unsigned)__popcll(bal & ((1ull << lane) - 1ull)) << (8 * (k & 3));
@@ -451,10 +505,7 @@ __device__ __forceinline__ void select_row_wide(const SelectParams& p, int b, Ma
             }
         }
     }
-    const int total = pad_rows(p.pose0 + b, n, kept, p.min_count, p.seed, [&](int i, int k) {
-        const Entry e = src.load(i);
-        rows.entry_from(base, k, e.u.x, e.u.y, e.s, e.X[0], e.X[1], e.X[2], e.src);
-    });  // test.py:108-113
+    const int total = pad_rows(p.pose0 + b, n, kept, p.min_count, p.seed, [&](int i, int k) { put(rows, base, k, src.load(i)); });  // test.py:108-113
     if (tid == 0) p.counts[b] = total;
     LC_FS_STAMP(5);
 }
@@ -466,31 +517,22 @@ template <typename T, typename TX, bool WIDE>
 __global__ __launch_bounds__(kThreads) void lc_dense_frontend_select_kernel(const SelectParams p, const DenseParams d) {
     extern __shared__ float srt[];
     __shared__ float red[kDenseLseThreads / kWave][2];
-    const int b = blockIdx.x, tid = threadIdx.x, HW = d.H * d.W;
-    MapSource<T, TX> src;
-    src.lg = static_cast<const T*>(d.wlogits) + (size_t)b * d.wl_bs;
-    src.xyz = d.xyz ? static_cast<const TX*>(d.xyz) + (size_t)b * d.xyz_bs : nullptr;
-    src.vis = d.vis_logits ? static_cast<const T*>(d.vis_logits) + (size_t)b * d.vis_bs : nullptr;
-    src.vis_thresh = d.vis_thresh;
-    src.HW = HW; src.W = d.W; src.top = d.top; src.left = d.left; src.sample = d.sample;
-    src.Wn = (d.W - d.left + d.sample - 1) / d.sample;
-    src.lse = 0.f;
-    src.scale = map_scalar_at(d.wscale, d.wscale_dtype, b);
-    for (int k = 0; k < 3; ++k) src.ns[k] = d.noc_scale ? d.noc_scale[3 * b + k] : 1.f;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    MapSource<T, TX> src = make_map_source<T, TX>(d, b);
     if (p.split_ws) {  // (uniform) the rescue launch behind a split launch: only the objects a part gave up on
         char* region = static_cast<char*>(p.split_ws) + (size_t)b * kSelSplitPoseBytes;
         const bool marked = xcd_load(split_tail(region, kSelSplitPoseBytes) + 1) != 0u;
         if (!split_rescue_enter(region, kSelSplitPoseBytes, marked, tid, kThreads)) return;
     }
     if constexpr (WIDE) {
-        select_row_wide(p, b, src, 2 * HW, red, srt);
+        select_row_wide(p, b, src, 2 * src.HW, red, srt);
     } else {
         Entry ec[kCache] = {};
         float vraw[kCache] = {};
 #pragma unroll
         for (int k = 0; k < kCache; ++k)
             if (tid + k * kThreads < p.N) ec[k] = src.fetch(tid + k * kThreads, vraw[k]);  // in flight while the log-sum-exp is formed
-        src.lse = block_lse<kDenseLseThreads>(src.lg, 2 * HW, red);
+        src.lse = block_lse<kDenseLseThreads>(src.lg, 2 * src.HW, red);
 #pragma unroll
         for (int k = 0; k < kCache; ++k) ec[k] = src.finish(ec[k], vraw[k]);
         select_row(p, b, p.N, src, ec, srt);
@@ -548,18 +590,9 @@ __global__ __launch_bounds__(kThreads) void lc_dense_frontend_select_split_kerne
     __shared__ int hist[3][256], merged[3][256];
     __shared__ int cnt[kCache][kWaves];
     const int P = p.split_parts, b = blockIdx.x / P, part = blockIdx.x % P;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, HW = d.H * d.W, n = p.N;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = p.N;
     const size_t base = (size_t)b * p.N;
-    MapSource<T, TX> src;
-    src.lg = static_cast<const T*>(d.wlogits) + (size_t)b * d.wl_bs;
-    src.xyz = d.xyz ? static_cast<const TX*>(d.xyz) + (size_t)b * d.xyz_bs : nullptr;
-    src.vis = d.vis_logits ? static_cast<const T*>(d.vis_logits) + (size_t)b * d.vis_bs : nullptr;
-    src.vis_thresh = d.vis_thresh;
-    src.HW = HW; src.W = d.W; src.top = d.top; src.left = d.left; src.sample = d.sample;
-    src.Wn = (d.W - d.left + d.sample - 1) / d.sample;
-    src.lse = 0.f;
-    src.scale = map_scalar_at(d.wscale, d.wscale_dtype, b);
-    for (int k = 0; k < 3; ++k) src.ns[k] = d.noc_scale ? d.noc_scale[3 * b + k] : 1.f;
+    MapSource<T, TX> src = make_map_source<T, TX>(d, b);
     char* region = static_cast<char*>(p.split_ws) + (size_t)b * kSelSplitPoseBytes;
     unsigned* epoch = reinterpret_cast<unsigned*>(region + kSelSplitPoseBytes - 128);
     SplitSum sx{reinterpret_cast<unsigned long long*>(region), epoch, P, part, xcd_load(epoch), 0u, false};
@@ -580,7 +613,7 @@ __global__ __launch_bounds__(kThreads) void lc_dense_frontend_select_split_kerne
     const int per = kDenseLseThreads / P, wpp = per / kWave;  // threads / wavefronts of that reduction this part plays
     if (tid < per) {
         float m = -FLT_MAX, s = 0.f;
-        lse_thread_share<kDenseLseThreads, 8>(src.lg, 2 * HW, part * per + tid, m, s);
+        lse_thread_share<kDenseLseThreads, 8>(src.lg, 2 * src.HW, part * per + tid, m, s);
         lse_wave_merge(m, s);
         if (lane == 0) { red[wave][0] = m; red[wave][1] = s; }
     }
@@ -588,9 +621,8 @@ __global__ __launch_bounds__(kThreads) void lc_dense_frontend_select_split_kerne
     if (p.mode == 2) {
 #pragma unroll
         for (int k = 0; k < kCache; ++k)
-            if (have[k] && src.vis && (1.f / (1.f + expf(-vraw[k]))) > src.vis_thresh) ++segc;  // MapSource::finish's own test
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) segc += __shfl_xor(segc, m, kWave);
+            if (have[k] && src.vis && src.visible(vraw[k])) ++segc;
+        segc = wave_sum(segc);
         if (lane == 0) wave_seg[wave] = segc;
     }
     __syncthreads();
@@ -632,26 +664,20 @@ __global__ __launch_bounds__(kThreads) void lc_dense_frontend_select_split_kerne
     for (int g = 0; g < P; ++g) seg_total += seg_parts[g];
 #pragma unroll
     for (int k = 0; k < kCache; ++k) ec[k] = src.finish(ec[k], vraw[k]);
-    auto weight_of = [&](const Entry& e) { return (p.mode == 2 && !e.g) ? 0.f : e.s.x + e.s.y; };
+    auto weight_of = [&](const Entry& e) { return select_weight(p.mode, e.s, e.g); };
     // 2. the threshold (quantile_threshold above, the bins of every pass merged over the parts)
     float thr = -FLT_MAX;
     if (p.mode != 0) {
         unsigned key[kCache];
 #pragma unroll
         for (int k = 0; k < kCache; ++k) key[k] = have[k] ? weight_key(weight_of(ec[k])) : 0u;
-        float q = p.quantile;
-        if (p.mode == 2) q = 1.f - p.one_minus_q * ((float)seg_total / (float)n);
-        q = fminf(fmaxf(q, 0.f), 1.f);
-        const float rank = q * (float)(n - 1);
-        const float lo = floorf(rank), hi = ceilf(rank);
-        const int klo = (int)lo, khi = min((int)hi, n - 1);
+        const QuantileRank qr = quantile_rank(p, n, seg_total);
         LC_FS_STAMP(3);
         unsigned prefix = 0u, mask = 0u, found[2];
-        int k = klo, in_bin = 0, next_bin = 256;
+        int k = qr.klo; RadixPick pk{};
         for (int pass = 3; pass >= 0; --pass) {
             const int shift = 8 * pass, cur = (3 - pass) % 3, nxt = (cur + 1) % 3;
-            const int* all = merged[cur];  // the parts' bins added up (three in rotation, zeroed a pass ahead, like the histograms)
-            if (tid < 256) { hist[nxt][tid] = 0; merged[nxt][tid] = 0; }
+            if (tid < 256) { hist[nxt][tid] = 0; merged[nxt][tid] = 0; }  // (the parts' bins added up: three in rotation, zeroed a pass ahead, like the histograms)
 #pragma unroll
             for (int j = 0; j < kCache; ++j) hist_add(hist[cur], (key[j] >> shift) & 255u, have[j] && (key[j] & mask) == prefix, lane, pass == 3);
             __syncthreads();
@@ -659,49 +685,21 @@ __global__ __launch_bounds__(kThreads) void lc_dense_frontend_select_split_kerne
                 give_up();
                 return;
             }
-            // every wavefront: lane l owns bins 4l .. 4l+3, exclusive prefix over the lanes, then the bin holding rank k
-            const int c0 = all[4 * lane], c1 = all[4 * lane + 1], c2 = all[4 * lane + 2], c3 = all[4 * lane + 3];
-            const int mine4 = c0 + c1 + c2 + c3;
-            int incl = mine4;
-#pragma unroll
-            for (int dd = 1; dd < kWave; dd <<= 1) {
-                const int up = __shfl_up(incl, dd, kWave);
-                if (lane >= dd) incl += up;
-            }
-            const int excl = incl - mine4;
-            const bool hit = k >= excl && k < incl;  // exactly one lane
-            int r = k - excl, bin = 4 * lane, cb = c0;
-            if (r >= c0) { r -= c0; ++bin; cb = c1; if (r >= c1) { r -= c1; ++bin; cb = c2; if (r >= c2) { r -= c2; ++bin; cb = c3; } } }
-            const int owner = __ffsll((long long)__ballot(hit)) - 1;
-            bin = __shfl(bin, owner, kWave);
-            prefix |= (unsigned)bin << shift;
+            pk = radix_pick<true>(merged[cur], lane, k, pass == 0);
+            prefix |= (unsigned)pk.bin << shift;
             mask |= 255u << shift;
-            k = __shfl(r, owner, kWave);
-            if (pass == 0) {  // the bins are exact keys: how many copies of the found key, and the next key present under the same 24-bit prefix
-                in_bin = __shfl(cb, owner, kWave);
-                int nb = 256;
-                if (4 * lane + 3 > bin) {
-                    if (c3 > 0 && 4 * lane + 3 > bin) nb = 4 * lane + 3;
-                    if (c2 > 0 && 4 * lane + 2 > bin) nb = 4 * lane + 2;
-                    if (c1 > 0 && 4 * lane + 1 > bin) nb = 4 * lane + 1;
-                    if (c0 > 0 && 4 * lane > bin) nb = 4 * lane;
-                }
-#pragma unroll
-                for (int mm = 32; mm >= 1; mm >>= 1) nb = min(nb, __shfl_xor(nb, mm, kWave));
-                next_bin = nb;
-            }
+            k = pk.rest;
         }
         found[0] = found[1] = prefix;
-        if (khi != klo && k + 1 >= in_bin) {  // (uniform) rank khi = klo + 1 is the next distinct key
-            if (next_bin < 256) {
-                found[1] = (prefix & ~255u) | (unsigned)next_bin;
+        if (qr.khi != qr.klo && k + 1 >= pk.in_bin) {  // (uniform) rank khi = klo + 1 is the next distinct key
+            if (pk.next_bin < 256) {
+                found[1] = (prefix & ~255u) | (unsigned)pk.next_bin;
             } else {  // none under this prefix: the smallest key above, over all parts
                 unsigned above = 0xFFFFFFFFu;
 #pragma unroll
                 for (int j = 0; j < kCache; ++j)
                     if (have[j] && key[j] > found[0]) above = min(above, key[j]);
-#pragma unroll
-                for (int mm = 32; mm >= 1; mm >>= 1) above = min(above, (unsigned)__shfl_xor((int)above, mm, kWave));
+                above = wave_min(above);
                 if (lane == 0) wave_above[wave] = above;
                 __syncthreads();
                 unsigned mine = 0xFFFFFFFFu;
@@ -715,8 +713,7 @@ __global__ __launch_bounds__(kThreads) void lc_dense_frontend_select_split_kerne
                 found[1] = above_min;
             }
         }
-        const float vlo = key_weight(found[0]), vhi = khi != klo ? key_weight(found[1]) : vlo;
-        thr = torch_lerp(vlo, vhi, rank - lo);
+        thr = quantile_value(found[0], found[1], qr);
     }
     LC_FS_STAMP(4);
     // 3. compaction: this part's survivors behind those of the parts before it
@@ -724,7 +721,7 @@ __global__ __launch_bounds__(kThreads) void lc_dense_frontend_select_split_kerne
     unsigned long long bal[kCache];
 #pragma unroll
     for (int k = 0; k < kCache; ++k) {
-        keep[k] = have[k] && (p.mode == 0 ? ec[k].g != 0 : (weight_of(ec[k]) >= thr && (p.mode == 1 || ec[k].g != 0)));
+        keep[k] = have[k] && select_keeps(p.mode, weight_of(ec[k]), ec[k].g, thr);
         bal[k] = __ballot(keep[k]);
         if (lane == 0) cnt[k][wave] = __popcll(bal[k]);
     }
@@ -748,18 +745,27 @@ __global__ __launch_bounds__(kThreads) void lc_dense_frontend_select_split_kerne
         if (g < part) before += kept_parts[g];
         kept += kept_parts[g];
     }
-    const RowCopy rows{nullptr, nullptr, nullptr, nullptr, p.o_pts2d, p.o_w, p.o_pts3d, p.o_index, p.square};
-    auto put = [&](const Entry& e, int o) { rows.entry_from(base, o, e.u.x, e.u.y, e.s, e.X[0], e.X[1], e.X[2], e.src); };
+    const RowCopy rows = select_rows(p);
 #pragma unroll
     for (int k = 0; k < kCache; ++k)
-        if (keep[k]) put(ec[k], before + off[k] + __popcll(bal[k] & ((1ull << lane) - 1ull)));
+        if (keep[k]) put(rows, base, before + off[k] + __popcll(bal[k] & ((1ull << lane) - 1ull)), ec[k]);
     if (part != 0) return;
-    const int total = pad_rows(p.pose0 + b, n, kept, p.min_count, p.seed, [&](int i, int k) { put(src.load(i), k); });  // test.py:108-113
+    const int total = pad_rows(p.pose0 + b, n, kept, p.min_count, p.seed, [&](int i, int k) { put(rows, base, k, src.load(i)); });  // test.py:108-113
     LC_FS_STAMP(6);
     if (tid == 0) {
         p.counts[b] = total;
         xcd_store(sx.epoch, sx.base + sx.seq);  // the tickets of this object's next launch count on from here
     }
+}
+
+// Host: a launch's dynamic LDS (the row's keys in modes 1, 2: a power of two, at least `least`), and the request a kernel has to make for more than 48 KB
+size_t select_keys_lds_bytes(const SelectParams& p, int least) {
+    int P = least;
+    while (P < p.N) P <<= 1;
+    return p.mode == 0 ? 0 : (size_t)P * sizeof(float);
+}
+bool allow_dynamic_lds(const void* kernel, size_t lds) {
+    return lds <= 48 * 1024 || hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
 }
 
 }  // namespace
@@ -773,13 +779,9 @@ size_t dense_select_split_workspace_bytes(int B, int N) { return dense_select_sp
 
 int launch_dense_select(const SelectParams& p, hipStream_t stream) {
     if (p.B <= 0) return 0;
-    int P = 1;
-    while (P < p.N) P <<= 1;
-    const size_t lds = p.mode == 0 ? 0 : (size_t)P * sizeof(float);
+    const size_t lds = select_keys_lds_bytes(p, 1);
     if (lds > 128 * 1024) return 3;
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(lc_dense_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return 2;
+    if (!allow_dynamic_lds(reinterpret_cast<const void*>(lc_dense_select_kernel), lds)) return 2;
     hipLaunchKernelGGL(lc_dense_select_kernel, dim3(p.B), dim3(kThreads), lds, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
@@ -788,16 +790,13 @@ int launch_dense_frontend_select(const SelectParams& p, const DenseParams& d_in,
     if (p.B <= 0) return 0;
     const DenseParams d = with_dense_strides(d_in);
     if (p.N > kFusedSelectMaxPoints) return 3;
-    int P = kThreads;
-    while (P < p.N) P <<= 1;
-    const size_t lds = p.mode == 0 ? 0 : (size_t)P * sizeof(float);
+    const size_t lds = select_keys_lds_bytes(p, kThreads);
     if (d.xyz_dtype != d.map_dtype && d.xyz_dtype != kMapF32) return 2;
     int rc = 0;
     bool rescue = false;
     SelectParams pr;
     auto go = [&](auto* kernel) {
-        if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            rc = 2;
+        if (!allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds)) rc = 2;
         else hipLaunchKernelGGL(kernel, dim3(p.B), dim3(kThreads), lds, stream, pr, d);
     };
     if (p.split_ws) {

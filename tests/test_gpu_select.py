@@ -241,3 +241,101 @@ def test_fp32_coordinates_next_to_16bit_logits_select_what_fp32_logits_select(B,
                 if name:
                     m = live if x.dim() == 2 else live[..., None].expand_as(x)
                     assert torch.equal(x[m], y[m]), (mode, split, name)
+
+
+# ---- which way the upper order statistic (rank klo + 1) of torch.quantile is found: host-side classification of a case ---------------------
+def weight_keys(w):
+    """The kernels' order-preserving integer image of fp32 weights (lc_select.hip: weight_key), as a numpy uint32 array."""
+    u = np.ascontiguousarray(w, dtype=np.float32).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def quantile_in_mask_q(quantile, seg_total, n):
+    """The kernels' mode-2 quantile 1 - (1 - q) * seg_total / n: fp32 operands, the product and the difference rounded once (one contracted
+    expression in the source; the product of two fp32 is exact in fp64).  A model, not a check: it assumes that the compiler contracts the
+    expression and that the host passes fp32(1 - q).  If either differs, q moves by an ulp and a case may change its class; the classification
+    is approximate in this respect, and the floor of three cases per class has wide slack."""
+    one_minus_q = np.float32(1.0 - quantile)
+    ratio = np.float32(seg_total) / np.float32(n)
+    return np.float32(1.0 - float(one_minus_q) * float(ratio))
+
+
+def upper_rank_class(sorted_keys, q):
+    """How rank khi = klo + 1 around fp32(q) * fp32(n - 1) relates to rank klo in the ascending keys of a row: 'integral' (no upper rank),
+    'duplicate' (the same key again), 'near' (another key under the same 24-bit prefix) or 'far'."""
+    n = len(sorted_keys)
+    q = np.float32(min(max(np.float32(q), np.float32(0)), np.float32(1)))
+    rank = np.float32(q * np.float32(n - 1))
+    klo, khi = int(np.floor(rank)), min(int(np.ceil(rank)), n - 1)
+    if khi == klo:
+        return "integral"
+    a, b = int(sorted_keys[klo]), int(sorted_keys[khi])
+    if a == b:
+        return "duplicate"
+    return "near" if a >> 8 == b >> 8 else "far"
+
+
+def ladder_inputs(H, W):
+    """Three objects on the host: random logits; all logits equal (every key equal); a ladder whose neighbouring weights lie a few to a few
+    hundred ulps apart (many neighbours share a 24-bit key prefix, many do not).  fp32 only: 16-bit logits collapse the ladder into duplicates."""
+    g = torch.Generator().manual_seed(H * 1000 + W)
+    B = 3
+    xyz = torch.randn(B, 3, H, W, generator=g)
+    wl = torch.randn(B, 2, H, W, generator=g) * 1.5
+    wl[1] = 0.25
+    wl[2, 0] = 0.0
+    wl[2, 1] = (-4.0 - torch.arange(H * W, dtype=torch.float64) * 4.0 / (H * W)).float().view(H, W)
+    yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+    blob = (((yy - H / 2) / (0.3 * H)) ** 2 + ((xx - W / 2) / (0.25 * W)) ** 2 < 1).float()
+    vl = (blob * 2 - 1) * 3 + torch.randn(B, 1, H, W, generator=g)
+    vl[2] = 9.0
+    ws = torch.full((B,), 3000.0)
+    ns = torch.rand(B, 3, generator=g) + 0.5
+    return xyz, wl, ws, ns, vl
+
+
+QUANTILES = [round(0.05 * k, 2) for k in range(1, 20)]
+
+
+@pytest.mark.parametrize("H,W,has_split", [(32, 32, False), (65, 64, True), (128, 128, True)])
+def test_upper_order_statistic_found_each_way_in_every_form(H, W, has_split):
+    """Rank klo + 1 of the quantile is the same key again, the next key under the same 24-bit prefix (read off the last pass' bins by the
+    several-workgroups form) or a key further up (one more meeting there): each of the three occurs at least three times among the cases of a
+    shape, classified on the host from the device's own weights -- and in every case the two launches, the one launch and (4160 and 16 384
+    candidates) the several-workgroups form agree bit for bit, and select what the oracle selects."""
+    from lc_amd import _lib
+    from lc_amd.dense import dense_front_end_select, dense_front_end_with_visibility, dense_select
+    from oracle import select_oracle as orc
+
+    xyz, wl, ws, ns, vl = (t.to(DEV) for t in ladder_inputs(H, W))
+    B, N = 3, H * W
+    assert (_lib.load().lc_dense_frontend_select_workspace_bytes(B, H, W, 0, 0, 1) > 0) == has_split
+    u, s, x, vis = dense_front_end_with_visibility(xyz, wl, ws, ns, vl, 0.5, sample=1)
+    s_h, vis_h = s.cpu(), vis.cpu()
+    live_of = lambda cnt: torch.arange(N, device=DEV)[None, :] < cnt[:, None]
+    seen = {"integral": 0, "duplicate": 0, "near": 0, "far": 0}
+    for mode in ("quantile", "quantile_in_mask"):
+        w_h = (s_h * vis_h[..., None]).sum(-1) if mode == "quantile_in_mask" else s_h.sum(-1)
+        keys = [np.sort(weight_keys(w_h[b].numpy())) for b in range(B)]
+        for q in QUANTILES:
+            kw = dict(quantile=q, square_weights=True, min_count=0, seed=5)
+            want = dense_select(u, s, x, mode, mask=vis, **kw)
+            forms = [("one launch", dense_front_end_select(xyz, wl, ws, ns, vl, mode, seg_thresh=0.5, sample=1, split=False, **kw))]
+            if has_split:
+                forms.append(("several workgroups", dense_front_end_select(xyz, wl, ws, ns, vl, mode, seg_thresh=0.5, sample=1, split=True, **kw)))
+            cnt = want[3]
+            live = live_of(cnt)
+            for form, got in forms:
+                assert torch.equal(got[3], cnt), (form, mode, q, got[3].tolist(), cnt.tolist())
+                for k, name in ((0, "pts2d"), (1, "weights"), (2, "pts3d"), (4, "index")):
+                    m = live if got[k].dim() == 2 else live[..., None].expand_as(got[k])
+                    assert torch.equal(got[k][m], want[k][m]), (form, mode, q, name)
+            exp = orc.select_mask(s_h, vis_h, mode, q).numpy()
+            o_c, o_i = want[3].cpu(), want[4].cpu()
+            for b in range(B):
+                idx = np.flatnonzero(exp[b])
+                assert int(o_c[b]) == len(idx) and np.array_equal(o_i[b, :len(idx)].numpy(), idx), (mode, q, b)
+                qb = quantile_in_mask_q(q, int(vis_h[b].sum()), N) if mode == "quantile_in_mask" else np.float32(q)
+                seen[upper_rank_class(keys[b], qb)] += 1
+    print(f"{H}x{W}: {seen}")
+    assert min(seen["duplicate"], seen["near"], seen["far"]) >= 3, seen

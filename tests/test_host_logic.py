@@ -466,3 +466,21 @@ def test_every_build_switch_is_listed_in_the_design():
     table = design[design.index("## 9. Build switches"):]
     listed = set(re.findall(r"^\| `(LC_\w+)` \|", table, re.M))
     assert len(in_sources) >= 10 and in_sources == listed, (sorted(in_sources - listed), sorted(listed - in_sources))
+
+
+def test_upper_rank_classifier_tells_duplicate_near_and_far_apart():
+    """The host-side classifier behind tests/test_gpu_select.py's coverage condition, on hand-made key lists: rank 1.5 of four keys lies
+    between keys[1] and keys[2]."""
+    from tests.test_gpu_select import quantile_in_mask_q, upper_rank_class, weight_keys
+
+    k = 0xBF800000
+    assert upper_rank_class(np.array([k - 9, k, k, k + 0x300], dtype=np.uint32), 0.5) == "duplicate"
+    assert upper_rank_class(np.array([k - 9, k, k + 0xFF, k + 0x300], dtype=np.uint32), 0.5) == "near"  # same upper 24 bits
+    assert upper_rank_class(np.array([k - 9, k + 0xFF, k + 0x100, k + 0x300], dtype=np.uint32), 0.5) == "far"  # one apart, across the prefix
+    assert upper_rank_class(np.array([k, k, k + 1, k + 1, k + 2], dtype=np.uint32), 0.5) == "integral"  # rank 2.0
+    assert upper_rank_class(np.array([k, k + 1], dtype=np.uint32), 1.5) == "integral"  # q clamped to 1: rank n - 1
+    # the keys ascend with the weights (negative ones below zero below positive ones) and the mode-2 quantile is the kernels' fp32 value
+    w = np.array([-2.0, -0.0, 0.0, 1e-30, 0.5, 0.5000001, 3.0], dtype=np.float32)
+    keys = weight_keys(w)
+    assert keys.dtype == np.uint32 and np.all(np.diff(keys.astype(np.int64)) > 0)
+    assert quantile_in_mask_q(0.2, 1024, 4096) == np.float32(0.8) and quantile_in_mask_q(0.2, 0, 7) == np.float32(1.0)
