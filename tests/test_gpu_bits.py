@@ -297,3 +297,129 @@ def test_bits_more_than_65535_samples_take_the_generic_forward(dtype):
     (go,) = torch.autograd.grad(ref, x64, ct.double())
     rnd = {torch.float32: 0.0, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}[dtype]  # half an ulp of the gradient's type, relative
     assert ((gk.cpu().double() - go).abs() <= 5e-6 * go.abs().max() + rnd * go.abs()).all()
+
+
+def _oracle_floor(bound, f32, f64):
+    """The file's bound, or twice the error of the oracle's own fp32 run against its fp64 run where that is larger."""
+    return max(bound, 2.0 * rel_err(f32, f64))
+
+
+# every axis length at which a walk of the channels changes: the smallest axis, the ends of the first, second and third round of eight, the C ABI's limit
+ROUND_EDGE_BITS = [[1, 8, 9], [16, 17, 1], [24, 1, 8]]
+
+
+def _bits_id(bits):
+    return "-".join(str(b) for b in bits)
+
+
+@pytest.mark.parametrize("H,W", [(3, 8), (3, 5)], ids=["3x8", "3x5"])  # four pixels per thread / one pixel per thread
+@pytest.mark.parametrize("bits", ROUND_EDGE_BITS, ids=_bits_id)
+def test_gray_decode_at_every_round_edge(bits, H, W):
+    """The inference (Gray) decode on axes of 1, 8, 9, 16, 17 and 24 bits -- decode_gray's first round alone, its second and its third --
+    through the three forms that share its pixel body: `nn_logits2noc` against the fp64 oracle, `nn_logits2xyz_planes` against
+    `nn_out_to_xyz(..., inference=True)`, `decode_selected_rows` against the planes gathered at a permutation of every pixel (a sample
+    with count 0 and everything behind a count left alone); fp16 / bf16 logits: the fp32 kernels on the up-cast values, bit for bit."""
+    from lc_amd import floatbits as fb
+    from lc_amd.losses import nn_out_to_xyz
+    from oracle import floatbits_oracle as orc
+
+    g = torch.Generator().manual_seed(sum(b * 31 ** i for i, b in enumerate(bits)) + W)
+    B, C, N = 2, sum(bits), H * W
+    dev = torch.device("cuda:0")
+    lg = torch.randn(B, C, H, W, generator=g)
+    scale = (torch.rand(B, 3, generator=g) * 100 + 20).to(dev)
+    q, _ = torch.linalg.qr(torch.randn(B, 3, 3, generator=g))
+    T = torch.eye(4).repeat(B, 1, 1)
+    T[:, :3, :3] = q
+    T[:, :3, 3] = torch.randn(B, 3, generator=g) * 5
+    T = T.to(dev)
+    index = torch.stack([torch.randperm(N, generator=g) for _ in range(B)]).int().to(dev)
+    counts = torch.tensor([0, N], dtype=torch.int32, device=dev)
+    sentinel = -12345.0
+
+    def rows(x, xf):
+        out = torch.full((B, N, 3), sentinel, device=dev)
+        return fb.decode_selected_rows(x, bits, index, counts, out, noc_scale=scale, model_transform=xf)
+
+    def gathered(planes):  # (B,3,H,W) -> (B,N,3) in the order of `index`, the sentinel behind each sample's count
+        pts = torch.gather(planes.flatten(2), 2, index.long()[:, None, :].expand(B, 3, N)).mT.contiguous()
+        return torch.where((torch.arange(N, device=dev)[None, :] < counts[:, None])[..., None], pts, torch.full_like(pts, sentinel))
+
+    x = lg.to(dev)
+    ref64 = orc.nn_logits2noc(lg.double(), bits)
+    bound = _oracle_floor(2e-6, orc.nn_logits2noc(lg, bits), ref64)  # 2e-6 in every case: the oracle's fp32 run is within 1.2e-7 of its fp64 run
+    noc = fb.nn_logits2noc(x, bits)
+    err = rel_err(noc.cpu(), ref64)
+    print(f"gray decode {bits} {H}x{W}: rel_err {err:.3g}, bound {bound:.3g}")
+    assert noc.shape == (B, H, W, 3) and err <= bound
+    planes = fb.nn_logits2xyz_planes(x, bits, scale, None)
+    assert torch.equal(planes, nn_out_to_xyz(x, scale, model_transform=None, bit_cnt=bits, inference=True).permute(0, 3, 1, 2).contiguous())
+    planes_T = fb.nn_logits2xyz_planes(x, bits, scale, T)
+    want_T = nn_out_to_xyz(x, scale, model_transform=T, bit_cnt=bits, inference=True).permute(0, 3, 1, 2)
+    assert (planes_T - want_T).abs().max() <= 2e-5 * want_T.abs().max()
+    assert torch.equal(rows(x, None), gathered(planes)) and torch.equal(rows(x, T), gathered(planes_T))
+    for dt in (torch.float16, torch.bfloat16):
+        xh = x.to(dt)
+        xf = xh.float()
+        assert torch.equal(fb.nn_logits2noc(xh, bits), fb.nn_logits2noc(xf, bits))
+        for xform in (None, T):
+            assert torch.equal(fb.nn_logits2xyz_planes(xh, bits, scale, xform), fb.nn_logits2xyz_planes(xf, bits, scale, xform))
+            assert torch.equal(rows(xh, xform), rows(xf, xform))
+
+
+@pytest.mark.parametrize("H,W,sample,tl", [
+    (5, 16, 1, (0, 0)),  # forward and backward: the flat kernels, four pixels per thread
+    (5, 5, 1, (0, 0)),   # the wide forward; the flat backward, one pixel per thread
+    (5, 16, 2, (1, 0)),  # the wide forward; the tiled backward (16 / 4 = 4 pieces per row for fp32, 16 / 8 = 2 for the 16-bit types), a partial last tile
+], ids=["5x16", "5x5", "5x16_s2"])
+@pytest.mark.parametrize("bits", ROUND_EDGE_BITS[1:], ids=_bits_id)
+def test_training_decode_at_every_round_edge(bits, H, W, sample, tl):
+    """The training decode on axes of 1, 8, 16, 17 and 24 bits (9: `[9, 10, 3]` in test_strided_training_decode_launch_forms) -- one, two
+    and three rounds of eight channels -- through every kernel that walks them, with an object mask: values and logit gradients of the fp32 kernels against the fp64 oracle, no gradient off the
+    sampled pixels; fp16 / bf16 logits: the fp32 kernels on the up-cast values, bit for bit (gradient: rounded once to the map's type).
+    One logit in twenty contradicts its ground-truth bit, so that the first wrong bit of an axis falls into each of its rounds."""
+    from lc_amd import floatbits as fb
+    from oracle import floatbits_oracle as orc
+
+    g = torch.Generator().manual_seed(sum(b * 31 ** i for i, b in enumerate(bits)) + H * W + sample)
+    B = 2
+    noc = torch.rand(B, H, W, 3, generator=g) * 2 - 1
+    mod, raw = fb.nn_noc2target(noc, bits)
+    lg = (mod.float() * 2 - 1) * (torch.rand(B, sum(bits), H, W, generator=g) * 3 + 0.1)
+    lg = torch.where(torch.rand(lg.shape, generator=g) < 0.05, -lg, lg)
+    msk = torch.rand(B, H, W, generator=g) > 0.3
+    dev = torch.device("cuda:0")
+    sl = (Ellipsis, slice(tl[0], None, sample), slice(tl[1], None, sample))
+
+    def oracle(dtype):
+        xo = lg.to(dtype).requires_grad_(True)
+        out = orc.nn_logits2noc_with_gt(xo[sl], raw[sl], bits, msk[sl]).flatten(1, 2)
+        return xo, out
+
+    x64, ref = oracle(torch.float64)
+    x32, ref32 = oracle(torch.float32)
+    ct = torch.randn(ref.shape, generator=g)
+    (go,), (go32,) = torch.autograd.grad(ref, x64, ct.double()), torch.autograd.grad(ref32, x32, ct)
+    # 2e-6 and 5e-6 in every case: the oracle's fp32 run is within 1.4e-7 (values) and 1.6e-7 (gradients) of its fp64 run
+    bound_v, bound_g = _oracle_floor(2e-6, ref32.detach(), ref.detach()), _oracle_floor(5e-6, go32, go)
+    x = lg.to(dev).requires_grad_(True)
+    out = fb.decode_with_gt_strided(x, raw.to(dev), bits, msk.to(dev), sample=sample, top_left=tl)
+    (gk,) = torch.autograd.grad(out, x, ct.to(dev))
+    err_v, err_g = rel_err(out.detach().cpu(), ref.detach()), rel_err(gk.cpu(), go)
+    print(f"training decode {bits} {H}x{W} sample {sample}: values {err_v:.3g} (bound {bound_v:.3g}), gradients {err_g:.3g} (bound {bound_g:.3g})")
+    assert out.shape == ref.shape and err_v <= bound_v
+    assert err_g <= bound_g
+    off = torch.ones(H, W, dtype=torch.bool)
+    off[tl[0]::sample, tl[1]::sample] = False
+    if off.any():
+        assert float(gk[..., off.to(dev)].abs().max()) == 0.0  # nothing off the sampled pixels
+    for dt in (torch.float16, torch.bfloat16):
+        xh = lg.to(dev).to(dt).requires_grad_(True)
+        xf = xh.detach().float().requires_grad_(True)
+        oh = fb.decode_with_gt_strided(xh, raw.to(dev), bits, msk.to(dev), sample=sample, top_left=tl)
+        of = fb.decode_with_gt_strided(xf, raw.to(dev), bits, msk.to(dev), sample=sample, top_left=tl)
+        assert torch.equal(oh, of)
+        (gh,), (gf,) = torch.autograd.grad(oh, xh, ct.to(dev)), torch.autograd.grad(of, xf, ct.to(dev))
+        assert gh.dtype == dt and torch.equal(gh, gf.to(dt))
+        if off.any():
+            assert float(gh[..., off.to(dev)].abs().max()) == 0.0
