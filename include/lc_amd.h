@@ -449,11 +449,33 @@ int lc_xyz_bin_loss_finish(const long long *counts, const float *bce_mean, int C
  * lc_label_targets_f32: xyz_gt (B,H,W,3) = R^T (K^-1 h - t) * msk_noc for Rt (B,3,4), cam_K (B,3,3), homo_z (B,H,W,3); then the targets of
  *   xyz_to_nn_target (losses.py:49-67): the model transform xform (B,4,4) or NULL, / noc_scale (B,3), and noc_tgt (B,3,H,W) f32 and/or the
  *   code planes bin_tgt (Gray code, planes 0-1 of each axis inverted when black_background) / bin_raw (B,n0+n1+n2,H,W) as bytes 0 / 1.
- *   msk_noc as bytes or floats (at most one; none: no mask).  Every output may be NULL. */
+ *   msk_noc as bytes or floats (at most one; none: no mask).  Every output may be NULL.
+ * The symmetry table (lc_amd.symmetry.SymmetrySet), device arrays: sym_tab (sym_rows,12) float64, one transform [R_s | t_s] per row as a
+ *   row-major 3 x 4 (8-byte aligned); object o owns rows [obj_off[o], obj_off[o] + obj_k[o]) (obj_off, obj_k: n_obj int32 each), and its
+ *   first row is the exact identity.  n_obj >= 1, 1 <= sym_rows < 2^31 / 12.  Candidate k of a batch row with base pose [R_b | t_b] =
+ *   Rt_base[b] (B,3,4 float32, widened to float64) and object o = obj_index[b] (B int32) is, for k = 0, the base pose itself (copied), and
+ *   for k >= 1, with S = row obj_off[o] + k, every product and sum rounded on its own (no fma) in this order and the result rounded once to
+ *   float32:   R_c[i][j] = ((R_b[i][0] S[0][j] + R_b[i][1] S[1][j]) + R_b[i][2] S[2][j]),
+ *              t_c[i]    = (((R_b[i][0] S[0][3] + R_b[i][1] S[1][3]) + R_b[i][2] S[2][3]) + t_b[i]).
+ *   A row whose obj_index lies outside [0, n_obj), or whose obj_off / obj_k leave the table, reads nothing of it (see each call).
+ * lc_sym_candidates_f32: Rt_candi of a batch.  The obj_k[o] candidates of row b -> rows [row_off[b], row_off[b] + obj_k[o]) of out
+ *   (out_rows,3,4) float32; row_off (B) int32 on the device, both 4-byte aligned.  1 <= out_rows < 2^31 / 12.  A row outside the table,
+ *   or whose range leaves out, is not written at all.  (A launch of the selection kernel that stops after forming the candidates.)
+ * lc_sym_select_table_f32: lc_sym_select_f32 with every row's candidates formed in the kernel from the table instead of read from `cand`:
+ *   no chunk table, no limit on the number of distinct candidate counts, any order of objects within the batch.  mode and the arguments
+ *   from cam_K on are those of lc_sym_select_f32, with the same rules.  The same bits as lc_sym_candidates_f32 followed by
+ *   lc_sym_select_f32 on its output.  A row with one candidate is not walked: Rt_best = the base pose, best_idx = 0.  A row outside the
+ *   table: Rt_best = NaN, best_idx = -1. */
 int lc_sym_select_f32(const float *cand, const int *chunk_rows, const int *chunk_k, int nchunks, int mode, const float *cam_K,
                       const float *pts_a, const float *pts_b, const void *xyz_map, int map_dtype, long long map_bstride,
                       const float *noc_scale, const float *homo_z, const long long *ck, int B, int N, int H, int W, float *Rt_best,
                       int *best_idx, void *stream);
+int lc_sym_candidates_f32(const float *Rt_base, const int *obj_index, const double *sym_tab, const int *obj_off, const int *obj_k, int n_obj,
+                          int sym_rows, const int *row_off, int B, float *out, int out_rows, void *stream);
+int lc_sym_select_table_f32(const float *Rt_base, const int *obj_index, const double *sym_tab, const int *obj_off, const int *obj_k, int n_obj,
+                            int sym_rows, int mode, const float *cam_K, const float *pts_a, const float *pts_b, const void *xyz_map,
+                            int map_dtype, long long map_bstride, const float *noc_scale, const float *homo_z, const long long *ck, int B,
+                            int N, int H, int W, float *Rt_best, int *best_idx, void *stream);
 int lc_label_targets_f32(const float *homo_z, const unsigned char *msk_noc_u8, const float *msk_noc_f32, const float *Rt,
                          const float *cam_K, const float *noc_scale, const float *xform, int B, int H, int W, int n0, int n1, int n2,
                          int black_background, float *xyz_gt, float *noc_tgt, unsigned char *bin_tgt, unsigned char *bin_raw,

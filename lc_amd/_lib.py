@@ -66,6 +66,10 @@ _SIGNATURES = {
     # label preparation (lc_labels.hip): the chunk table is two HOST int arrays
     "lc_sym_select_f32": (c_int, [c_void_p, _I, _I, c_int, c_int] + [c_void_p] * 4 + [c_int, ctypes.c_longlong] + [c_void_p] * 3 + [c_int] * 4 +
                           [c_void_p] * 3),
+    # the same with the candidates formed from a SymmetrySet's device table (lc_amd/symmetry.py)
+    "lc_sym_candidates_f32": (c_int, [c_void_p] * 5 + [c_int] * 2 + [c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "lc_sym_select_table_f32": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p] * 4 + [c_int, ctypes.c_longlong] + [c_void_p] * 3 + [c_int] * 4 +
+                                [c_void_p] * 3),
     "lc_label_targets_f32": (c_int, [c_void_p] * 7 + [c_int] * 7 + [c_void_p] * 5),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -12,9 +12,11 @@
 #include <cstdint>
 
 #include "lc_host_stage.h"
+#include "lc_sym_args.h"
 
 static_assert(LC_ARRIVAL_WORDS == lc::kArrivalWords, "include/lc_amd.h and lc_common.h disagree on the arrival counters");
 #include "lc_kernels.h"
+static_assert(lc::host::kSymArgMaxPoints == lc::kSymMaxPoints, "lc_sym_args.h and lc_kernels.h disagree on the check points of a selection");
 
 #ifndef LC_AMD_SRC_HASH
 #define LC_AMD_SRC_HASH "unrecorded"
@@ -719,9 +721,7 @@ int lc_xyz_bin_loss_bwd2(const void* logits, const unsigned char* gt_bits, const
 int lc_sym_select_f32(const float* cand, const int* chunk_rows, const int* chunk_k, int nchunks, int mode, const float* cam_K, const float* pts_a,
                       const float* pts_b, const void* xyz_map, int map_dtype, long long map_bstride, const float* noc_scale, const float* homo_z,
                       const long long* ck, int B, int N, int H, int W, float* Rt_best, int* best_idx, void* stream) {
-    if (B < 0 || N <= 0 || H < 0 || W < 0) return fail(1, "bad size");
-    if (N > lc::kSymMaxPoints) return fail(1, "more than 1024 check points per sample");
-    if (mode != 0 && mode != 1) return fail(1, "mode must be 0 (2D) or 1 (3D)");
+    if (const char* e = lc::host::sym_select_size_error(mode, B, N, H, W)) return fail(1, e);
     if (nchunks <= 0 || nchunks > lc::kSymMaxChunks) return fail(1, "between 1 and 32 candidate chunks");
     if (!chunk_rows || !chunk_k) return fail(1, "null chunk table");
     if (chunk_rows[0] != 0 || chunk_rows[nchunks] != B) return fail(1, "chunk rows must start at 0 and end at B");
@@ -738,26 +738,44 @@ int lc_sym_select_f32(const float* cand, const int* chunk_rows, const int* chunk
     }
     p.chunk_row[nchunks] = B;
     if (B == 0) return 0;
-    if (!cand || !cam_K || !Rt_best) return fail(1, "null pointer");
-    if (mode == 0) {
-        if (!pts_a || !pts_b) return fail(1, "2D mode needs pts3d and pts2d");
-    } else {
-        if (!pts_a && (!xyz_map || !noc_scale)) return fail(1, "3D mode needs the predicted points or the xyz map with noc_scale");
-        if (!pts_b && !homo_z) return fail(1, "3D mode needs homo_z at the points or the homo_z map");
-        if (!pts_a || !pts_b) {
-            if (!ck) return fail(1, "reading a map needs the check pixels");
-            if (H <= 0 || W <= 0) return fail(1, "bad map size");
-            if ((long long)B * H * W * 3 >= (1ll << 31)) return fail(1, "maps of 2^31 elements or more");
-        }
-        if (!pts_a) {
-            if (map_dtype < 0 || map_dtype > 2) return fail(1, "map_dtype must be LC_F32, LC_F16 or LC_BF16");
-            if (map_bstride < 0 || (map_bstride && map_bstride < 3ll * H * W)) return fail(1, "batch stride smaller than a sample");
-        }
-    }
+    if (!cand) return fail(1, "null pointer");
+    if (const char* e = lc::host::sym_select_points_error(mode, cam_K, pts_a, pts_b, xyz_map, map_dtype, map_bstride, noc_scale, homo_z, ck, B, H, W,
+                                                          Rt_best))
+        return fail(1, e);
     p.nchunks = nchunks; p.cand = cand; p.mode = mode; p.cam_K = cam_K; p.pts_a = pts_a; p.pts_b = pts_b;
     p.xyz_map = xyz_map; p.map_dtype = map_dtype; p.map_bs = map_bstride ? map_bstride : 3ll * H * W; p.noc_scale = noc_scale;
     p.homo_z = homo_z; p.ck = ck; p.B = B; p.N = N; p.H = H; p.W = W; p.Rt_best = Rt_best; p.best_idx = best_idx;
     return lc::launch_sym_select(p, static_cast<hipStream_t>(stream)) ? fail(11, "symmetry selection launch failed") : 0;
+}
+
+int lc_sym_select_table_f32(const float* Rt_base, const int* obj_index, const double* sym_tab, const int* obj_off, const int* obj_k, int n_obj,
+                            int sym_rows, int mode, const float* cam_K, const float* pts_a, const float* pts_b, const void* xyz_map, int map_dtype,
+                            long long map_bstride, const float* noc_scale, const float* homo_z, const long long* ck, int B, int N, int H, int W,
+                            float* Rt_best, int* best_idx, void* stream) {
+    if (const char* e = lc::host::sym_select_size_error(mode, B, N, H, W)) return fail(1, e);
+    if (B == 0) return 0;
+    if (const char* e = lc::host::sym_table_error(Rt_base, obj_index, sym_tab, obj_off, obj_k, n_obj, sym_rows)) return fail(1, e);
+    if (const char* e = lc::host::sym_select_points_error(mode, cam_K, pts_a, pts_b, xyz_map, map_dtype, map_bstride, noc_scale, homo_z, ck, B, H, W,
+                                                          Rt_best))
+        return fail(1, e);
+    lc::SymSelectParams p{};
+    p.Rt_base = Rt_base; p.obj_index = obj_index; p.sym_tab = sym_tab; p.obj_off = obj_off; p.obj_k = obj_k; p.n_obj = n_obj; p.sym_rows = sym_rows;
+    p.mode = mode; p.cam_K = cam_K; p.pts_a = pts_a; p.pts_b = pts_b;
+    p.xyz_map = xyz_map; p.map_dtype = map_dtype; p.map_bs = map_bstride ? map_bstride : 3ll * H * W; p.noc_scale = noc_scale;
+    p.homo_z = homo_z; p.ck = ck; p.B = B; p.N = N; p.H = H; p.W = W; p.Rt_best = Rt_best; p.best_idx = best_idx;
+    return lc::launch_sym_select(p, static_cast<hipStream_t>(stream)) ? fail(11, "symmetry selection launch failed") : 0;
+}
+
+int lc_sym_candidates_f32(const float* Rt_base, const int* obj_index, const double* sym_tab, const int* obj_off, const int* obj_k, int n_obj,
+                          int sym_rows, const int* row_off, int B, float* out, int out_rows, void* stream) {
+    if (B < 0) return fail(1, "bad size");
+    if (B == 0) return 0;
+    if (const char* e = lc::host::sym_table_error(Rt_base, obj_index, sym_tab, obj_off, obj_k, n_obj, sym_rows)) return fail(1, e);
+    if (const char* e = lc::host::sym_candidates_out_error(row_off, out, out_rows)) return fail(1, e);
+    lc::SymSelectParams p{};
+    p.Rt_base = Rt_base; p.obj_index = obj_index; p.sym_tab = sym_tab; p.obj_off = obj_off; p.obj_k = obj_k; p.n_obj = n_obj; p.sym_rows = sym_rows;
+    p.cand_out = out; p.row_off = row_off; p.out_rows = out_rows; p.B = B;
+    return lc::launch_sym_candidates(p, static_cast<hipStream_t>(stream)) ? fail(11, "symmetry candidates launch failed") : 0;
 }
 
 int lc_label_targets_f32(const float* homo_z, const unsigned char* msk_noc_u8, const float* msk_noc_f32, const float* Rt, const float* cam_K,

@@ -387,8 +387,25 @@ struct SymSelectParams {
     int B, N, H, W;
     float* Rt_best;               // (B,3,4)
     int* best_idx;                // (B,) index within the row's candidates, or null
+    // Table form (non-null sym_tab; cand and the chunk table are unused): row b's candidates are formed in the kernel from its base pose
+    // and the obj_k[o] transforms of its object o = obj_index[b], rows [obj_off[o], obj_off[o] + obj_k[o]) of sym_tab (sym_candidate
+    // in lc_labels.hip).  A row whose o lies outside [0, n_obj), or whose range leaves sym_tab, gets NaN and index -1; nothing is read for it.
+    const float* Rt_base;         // (B,3,4) [R_no_aug | t_no_aug]
+    const int* obj_index;         // (B,)
+    const double* sym_tab;        // (sym_rows,12) [R_s | t_s] row-major 3 x 4; the first row of every object is the exact identity
+    const int* obj_off;           // (n_obj,)
+    const int* obj_k;             // (n_obj,)
+    int n_obj, sym_rows;
+    float* cand_out;              // launch_sym_candidates only, else null
+    const int* row_off;           // (B,)
+    int out_rows;
 };
 int launch_sym_select(const SymSelectParams& p, hipStream_t stream);
+
+// Rt_candi of a batch from the table: with a non-null cand_out (and the table form's arrays) the launch only writes candidates -- the
+// obj_k[obj_index[b]] candidates of row b to rows [row_off[b], ...) of cand_out (out_rows,3,4) -- and selects nothing.  A row outside
+// the table, or whose range leaves cand_out, is not written.
+int launch_sym_candidates(const SymSelectParams& p, hipStream_t stream);
 
 // Label targets: xyz_gt = R^T (K^-1 h - t) * m over B x H x W, then the network targets of xyz_to_nn_target (losses.py:49-67)
 struct LabelParams {

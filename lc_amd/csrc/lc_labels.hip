@@ -6,7 +6,13 @@
 //     points in index order, the wave sums by a fixed butterfly (wave_allreduce), the mean is sum / N -- every candidate's error is
 //     a deterministic value, so duplicated candidates tie exactly.  The argmin is torch.argmin's: the smallest mean error, the first
 //     index among equal ones, and a NaN error wins at its first occurrence.  In 3D mode K^-1 h (independent of the candidate) is
-//     computed once per point in fp64 and kept as fp32.
+//     computed once per point in fp64 and kept as fp32.  The candidates come from the caller's array (the chunk table), or -- table form
+//     -- are formed from the row's base pose and its object's symmetry transforms (sym_candidate) while they are staged in LDS:
+//     12 outputs x 5 fp64 operations per candidate spread over the workgroup, a few per cent of the walk that follows.  A row of more
+//     than kSelLdsCands candidates forms each one in the walk instead (every lane of the wave the same 12 values): no second launch, no
+//     host knowledge of the batch's objects and no limit on the batch, at ~60 redundant fp64 operations per candidate and wave next to
+//     the ~35 per check point the walk spends anyway.  With p.cand_out set the workgroup writes the row's candidates to global memory
+//     instead of LDS and stops (lc_sym_candidates_f32, Rt_candi): the same loop, consecutive threads storing consecutive floats.
 // (B) lc_label_targets_kernel: one streaming pass over B x H x W -- xyz_gt = R^T (K^-1 h - t) * m (fp64, stored fp32), then
 //     xyz_to_nn_target: the model transform (and the mask again), / noc_scale, and the continuous target or the Gray-coded bit
 //     planes of floatbits.mod_noc2bits_bb (the quantiser argument (noc + 1) * (2^n - 1) / 2 in fp32 from the fp32 noc, as torch
@@ -51,6 +57,31 @@ __device__ __forceinline__ void row_candidates(const SymSelectParams& p, int b, 
         }
 }
 
+// row b's object in the table: number of transforms and the first one; K = 0 for a row the table does not hold (nothing of it is read)
+__device__ __forceinline__ void table_row(const int* obj_index, const int* obj_off, const int* obj_k, int n_obj, int sym_rows, int b, int& K,
+                                          int& off) {
+    K = 0; off = 0;
+    const int o = obj_index[b];
+    if (o < 0 || o >= n_obj) return;
+    const int k = obj_k[o], f = obj_off[o];
+    if (k < 1 || f < 0 || (long long)f + k > sym_rows) return;
+    K = k; off = f;
+}
+
+// Element e (row i = e / 4, column j = e % 4) of candidate k of a row: [R_b R_s | R_b t_s + t_b] for the base pose `base` (fp32, widened)
+// and transform k of the object (`sym`: its first transform; fp64), every product and sum rounded on its own (no fma), in this order:
+//   ((R_b[i][0] S[0][j] + R_b[i][1] S[1][j]) + R_b[i][2] S[2][j]) (+ t_b[i] for j = 3), then one rounding to fp32.
+// Transform 0 of every object is the identity: candidate 0 IS the base pose, copied (also its NaNs, infinities and signed zeros).
+__device__ __forceinline__ float sym_candidate(const float* base, const double* sym, int k, int e) {
+    if (k == 0) return base[e];
+    const int i = e >> 2, j = e & 3;
+    const double* S = sym + 12 * (size_t)k;
+    double v = __dadd_rn(__dadd_rn(__dmul_rn((double)base[4 * i], S[j]), __dmul_rn((double)base[4 * i + 1], S[4 + j])),
+                         __dmul_rn((double)base[4 * i + 2], S[8 + j]));
+    if (j == 3) v = __dadd_rn(v, (double)base[4 * i + 3]);
+    return (float)v;
+}
+
 template <int PPL, int THREADS>
 __global__ __launch_bounds__(THREADS) void lc_sym_select_kernel(const SymSelectParams p) {
     constexpr int kSelWaves = THREADS / kWave;
@@ -59,13 +90,27 @@ __global__ __launch_bounds__(THREADS) void lc_sym_select_kernel(const SymSelectP
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave, N = p.N;
     __shared__ float s_cand[12 * kSelLdsCands];
     int K, off;
-    row_candidates(p, b, K, off);
-    const float* cand = p.cand + (size_t)off * 12;
+    const bool table = p.sym_tab != nullptr;
+    if (table) table_row(p.obj_index, p.obj_off, p.obj_k, p.n_obj, p.sym_rows, b, K, off);
+    else row_candidates(p, b, K, off);
+    const float* cand = table ? nullptr : p.cand + (size_t)off * 12;
+    const float* base = table ? p.Rt_base + 12 * (size_t)b : nullptr;
+    const double* sym = table ? p.sym_tab + 12 * (size_t)off : nullptr;
+    if (p.cand_out) {  // materialise only (the whole grid takes this branch)
+        const int row = p.row_off[b];
+        if (row >= 0 && (long long)row + K <= p.out_rows)
+            for (int i = tid; i < 12 * K; i += THREADS) p.cand_out[12 * (size_t)row + i] = sym_candidate(base, sym, i / 12, i % 12);
+        return;
+    }
     // the row's candidates are staged in LDS by the whole workgroup: each wave walks its candidates one after the other, and a global
     // load per candidate in that loop would put the memory latency on the critical path of every iteration
     const bool staged = K > 1 && K <= kSelLdsCands;
-    if (staged)
-        for (int i = tid; i < 12 * K; i += THREADS) s_cand[i] = cand[i];
+    if (staged) {
+        if (table)
+            for (int i = tid; i < 12 * K; i += THREADS) s_cand[i] = sym_candidate(base, sym, i / 12, i % 12);
+        else
+            for (int i = tid; i < 12 * K; i += THREADS) s_cand[i] = cand[i];
+    }
     __syncthreads();
     const float* walk = staged ? s_cand : cand;
     const float nanf = __builtin_nanf("");
@@ -119,7 +164,14 @@ __global__ __launch_bounds__(THREADS) void lc_sym_select_kernel(const SymSelectP
 #pragma unroll
             for (int i = 0; i < 9; ++i) Kc[i] = p.cam_K[9 * (size_t)b + i];
         for (int k = wave; k < K; k += kSelWaves) {
-            const float* c = walk + 12 * k;
+            float c[12];
+            if (table && !staged) {
+#pragma unroll
+                for (int e = 0; e < 12; ++e) c[e] = sym_candidate(base, sym, k, e);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 12; ++e) c[e] = walk[12 * k + e];
+            }
             double R[9], t[3];
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
@@ -179,7 +231,8 @@ __global__ __launch_bounds__(THREADS) void lc_sym_select_kernel(const SymSelectP
                     be = s_e[w];
                     bk = s_k[w];
                 }
-        p.Rt_best[12 * (size_t)b + tid] = cand[12 * bk + tid];
+        if (table && K == 0) bk = -1;
+        p.Rt_best[12 * (size_t)b + tid] = !table ? cand[12 * bk + tid] : (K == 0 ? nanf : sym_candidate(base, sym, bk, tid));
         if (tid == 0 && p.best_idx) p.best_idx[b] = bk;
     }
 }
@@ -363,6 +416,12 @@ int launch_sym_select(const SymSelectParams& p, hipStream_t stream) {
     else if (p.N <= 8 * kWave) hipLaunchKernelGGL((lc_sym_select_kernel<8, kSelThreads>), grid, block, 0, stream, p);
     else if (p.N <= 16 * kWave) hipLaunchKernelGGL((lc_sym_select_kernel<16, 256>), grid, dim3(256), 0, stream, p);
     else return 3;
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+int launch_sym_candidates(const SymSelectParams& p, hipStream_t stream) {
+    if (p.B <= 0) return 0;
+    hipLaunchKernelGGL((lc_sym_select_kernel<1, kSelThreads>), dim3(p.B), dim3(kSelThreads), 0, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

@@ -27,6 +27,13 @@ Opt-in (`install(native_depth=MODELS_DIR)`, or `--native-depth MODELS_DIR`; impl
     annots_on_the_fly render `homo_z_out` for every batch that comes without it; dataset.BOP_Dataset._get_homo_with_depth no longer opens
     `z_path` and _get_single_item leaves `homo_z_out` out of its blob, so a training run needs no `z_crop` directory.
 
+Opt-in (`install(native_sym=MODELS_INFO_JSON)`, or `--native-sym MODELS_INFO_JSON`; implies `--native-labels`): the symmetric pose candidates --
+    the per-object symmetry transforms of `models_info.json` are uploaded once (lc_amd.symmetry.SymmetrySet, 384 steps of a continuous
+    symmetry as the reference) and `lc_amd.labels.set_symmetry_source` makes annots_on_the_fly form every row's candidates on the device from
+    R_no_aug, t_no_aug and obj_id; `symmetry.symmetry_pose_candidates` as the reference's `dataset` module calls it (dataset.py:405) returns
+    the single base pose [R | t][None], so the loader ships 12 floats per sample and `sym_collate` keeps the batch in order (one chunk).
+    Objects with a continuous AND discrete symmetries are served too (the reference itself raises for them).
+
 Opt-in (`install(native_crops=True)`, or `--native-crops`): the zoom-in crop of the test-time loader (the reference's `dataset` module must still import,
     which needs a cv2 module, imgaug and pycocotools: lc_amd.crops.test_item makes no OpenCV call, `import dataset` does) --
     dataset.BOP_Dataset._get_single_item of a dataset with `training == False` -> lc_amd.crops.test_item (the frame as uint8 and the
@@ -44,13 +51,14 @@ import types
 
 
 def install(patch_ptnet: bool = True, gpu_initialiser=None, native_labels: bool = False, native_optim: bool = False, native_depth=None,
-            native_crops: bool = False) -> dict:
+            native_crops: bool = False, native_sym=None) -> dict:
     """gpu_initialiser: True = also register the RANSAC-P3P kernel as `lib.pnp.cv2_solver` (same `solve` surface,
     `test.py:59,120`); None (default) = only when OpenCV cannot be imported, so that `test.py` runs without it.
     native_labels: also rebind the reference's label-preparation names to lc_amd.labels (done["labels"]).
     native_optim: also rebind the reference's Ranger to lc_amd.optim.Ranger (done["optim"]).
     native_depth: a directory of BOP models (obj_*.ply, in mm): also native_labels, with the labels' depth rendered from them (done["depth"]).
-    native_crops: also take the test-time loader's zoom-in crop onto the device (done["crops"])."""
+    native_crops: also take the test-time loader's zoom-in crop onto the device (done["crops"]).
+    native_sym: a BOP models_info.json: also native_labels, with the symmetric pose candidates formed on the device from it (done["sym"])."""
     from . import cov_mixed as cm
     from . import ptnet as head
     from .pnp import cer_solver, gpu_solver, pnp_ceres
@@ -122,8 +130,10 @@ def install(patch_ptnet: bool = True, gpu_initialiser=None, native_labels: bool 
             done["ptnet"] = True
         except Exception:
             done["ptnet"] = False
-    if native_labels or native_depth:
+    if native_labels or native_depth or native_sym:
         done["labels"] = _install_labels()
+    if native_sym:
+        done["sym"] = _install_sym(native_sym)
     if native_depth:
         done["depth"] = _install_depth(native_depth)
     if native_optim:
@@ -193,6 +203,43 @@ def _detach_loader_from_z_crop() -> bool:
     return True
 
 
+def _install_sym(models_info) -> bool:
+    """The symmetry transforms of `models_info` (a BOP models_info.json) on the current device as the labels' symmetry source, and the
+    reference's loader taken off the candidates: True only when the loader's name was rebound too."""
+    import torch
+
+    from . import labels, symmetry
+
+    labels.set_symmetry_source(symmetry.SymmetrySet.from_models_info(models_info, device=torch.device("cuda", torch.cuda.current_device())))
+    return _detach_loader_from_candidates()
+
+
+def _detach_loader_from_candidates() -> bool:
+    """Rebinds `symmetry_pose_candidates` of the module the reference's `dataset` calls it on (dataset.py:15,405) to return the base pose
+    alone, (1,3,4) (idempotent); False when neither `dataset` nor `symmetry` of the reference can be imported (then the caller's own loader
+    ships what it likes: `Rt_candi` is ignored while a symmetry source is set)."""
+    import numpy as np
+
+    try:
+        mod = importlib.import_module("dataset").symmetry
+    except Exception:  # the reference's loader needs cv2, imgaug, ...: the module it would call is the top-level `symmetry`
+        try:
+            mod = importlib.import_module("symmetry")
+        except Exception:
+            return False
+    if not hasattr(mod, "symmetry_pose_candidates"):
+        return False
+    if getattr(mod.symmetry_pose_candidates, "_lc_amd_native_sym", False):
+        return True
+
+    def symmetry_pose_candidates(base_R, base_t, model_info=None, continuous_steps=384):
+        return np.concatenate((np.asarray(base_R), np.asarray(base_t)[..., None]), axis=-1)[None]
+
+    symmetry_pose_candidates._lc_amd_native_sym = True
+    mod.symmetry_pose_candidates = symmetry_pose_candidates
+    return True
+
+
 def _install_crops() -> bool:
     """Rebinds the test-time loader and the transfer (idempotent); False when the reference's `dataset` or `utils` cannot be imported.
     `finish_blob` needs the size of the network's input, which no blob carries: the rebound `collate_fn` (called where the loader is
@@ -254,7 +301,7 @@ def _install_optim() -> bool:
 
 
 _FLAGS = ("--native-labels", "--native-optim", "--native-crops")
-_VALUE_FLAGS = ("--native-depth",)
+_VALUE_FLAGS = ("--native-depth", "--native-sym")
 
 
 def main(argv=None):
@@ -276,7 +323,8 @@ def main(argv=None):
     # native_optim (and native_crops) is passed only when asked for: without the flag install() gets exactly the arguments it got before the flag existed
     kw = dict(native_labels=native_labels, **({"native_optim": True} if native_optim else {}),
               **({"native_depth": values["--native-depth"]} if "--native-depth" in values else {}),
-              **({"native_crops": True} if "--native-crops" in flags else {}))
+              **({"native_crops": True} if "--native-crops" in flags else {}),
+              **({"native_sym": values["--native-sym"]} if "--native-sym" in values else {}))
     print("lc_amd.dropin:", install(**kw), file=sys.stderr)
     sys.argv = argv
     runpy.run_path(script, run_name="__main__")

@@ -14,6 +14,15 @@ be captured in a graph.  HIP tensors only; `lc_amd.dropin.install(native_labels=
 Opt-in depth source (`set_depth_source(meshes, near, far)`, `clear_depth_source()`; `lc_amd.dropin --native-depth MODELS_DIR`): a
 gt_dict WITHOUT the key `homo_z_out` gets it rendered on the device (lc_amd.render.render_homo_z_out from R_no_aug, t_no_aug, K_no_aug,
 out_K and obj_id; `msk_noc` too where it is absent).  With the key present nothing changes.
+
+Opt-in symmetry source (`set_symmetry_source(symset)`, `clear_symmetry_source()`; `lc_amd.dropin --native-sym MODELS_INFO_JSON`): the
+candidate poses are formed on the device from the base pose (R_no_aug, t_no_aug), `obj_id` and the per-object table of a
+lc_amd.symmetry.SymmetrySet, inside the selection launch (lc_sym_select_table_f32).  `Rt_candi` is IGNORED while a source is set (it need
+not be in gt_dict), every row takes its own candidate count from the table, and the step does not depend on the batch's mix of objects: one
+captured graph serves every batch.  A row whose obj_id the set lacks gets a NaN `Rt_best` (nothing is read back to refuse it on the host).
+
+    symmetry_pose_candidates(base_R, base_t, symset, obj_id)      -> (B,K,3,4)         lc_sym_candidates_f32 (the reference's `Rt_candi`)
+    symmetry_pose_candidates_list(base_R, base_t, symset, obj_id) -> [(K_b,3,4)] * B   the same for rows of different K
 """
 from __future__ import annotations
 
@@ -71,6 +80,75 @@ def _render_missing_depth(gt_dict, out_dict):
         gt_dict['msk_noc'] = msk
 
 
+_SYM_SOURCE = None  # lc_amd.symmetry.SymmetrySet
+
+
+def set_symmetry_source(symset):
+    """From now on `annots_on_the_fly` / `selete_best_pose` form the symmetric pose candidates on the device from R_no_aug, t_no_aug,
+    obj_id and `symset` (a lc_amd.symmetry.SymmetrySet whose obj_ids are the dataset's); gt_dict['Rt_candi'] is ignored."""
+    global _SYM_SOURCE
+    from . import symmetry
+
+    if not isinstance(symset, symmetry.SymmetrySet):
+        raise TypeError(f"lc_amd.labels: set_symmetry_source takes a lc_amd.symmetry.SymmetrySet, got {type(symset)}")
+    _SYM_SOURCE = symset
+
+
+def clear_symmetry_source():
+    global _SYM_SOURCE
+    _SYM_SOURCE = None
+
+
+def _table_args(symset):
+    return _lib.ptr(symset.table), _lib.ptr(symset.obj_off), _lib.ptr(symset.obj_k), symset.n_obj, symset.total
+
+
+def _base_pose(symset, base_R, base_t):
+    R, t = base_R.reshape(-1, 3, 3), base_t.reshape(-1, 3, 1)
+    return _f32("base pose", torch.cat((R, t), -1).to(symset.device))
+
+
+def _candidates(base_R, base_t, symset, obj_id):
+    """(flat (Ktot,3,4) float32, first row and candidate count of every batch row (host arrays))."""
+    index = symset.host_index_of(obj_id)
+    base = _base_pose(symset, base_R, base_t)
+    B = int(base.shape[0])
+    if len(index) != B:
+        raise ValueError(f"lc_amd.labels: {B} base poses and {len(index)} obj_ids")
+    ks = symset.obj_k_host[index].astype("int64")
+    offs = ks.cumsum() - ks
+    total = int(ks.sum())
+    dev = symset.device
+    out = torch.empty(total, 3, 4, device=dev, dtype=torch.float32)
+    if B:
+        idx = torch.as_tensor(index, dtype=torch.int32).to(dev)
+        row_off = torch.as_tensor(offs, dtype=torch.int32).to(dev)
+        with _lib.on_device(dev):
+            rc = _lib.load().lc_sym_candidates_f32(_lib.ptr(base), _lib.ptr(idx), *_table_args(symset), _lib.ptr(row_off), B,
+                                                   _lib.ptr(out), total, _lib.stream_ptr(dev))
+        _lib.check(rc, "lc_sym_candidates_f32")
+    return out, offs, ks
+
+
+@torch.no_grad()
+def symmetry_pose_candidates_list(base_R: Tensor, base_t: Tensor, symset, obj_id):
+    """`symmetry.py:58-93` for a batch, from the table: row b's (K_b,3,4) float32 candidates [R_b R_s | R_b t_s + t_b] (views of one
+    buffer).  Reads obj_id on the host for the shapes (one synchronising copy when it is a device tensor): not for the hot path, which
+    needs no materialised candidates.  An obj_id the set lacks raises."""
+    out, offs, ks = _candidates(base_R, base_t, symset, obj_id)
+    return [out[int(o):int(o + k)] for o, k in zip(offs, ks)]
+
+
+@torch.no_grad()
+def symmetry_pose_candidates(base_R: Tensor, base_t: Tensor, symset, obj_id) -> Tensor:
+    """(B,K,3,4): the candidates of a batch whose rows share one candidate count K (the reference's `Rt_candi` of one chunk)."""
+    out, offs, ks = _candidates(base_R, base_t, symset, obj_id)
+    if len(set(ks.tolist())) > 1:
+        raise ValueError(f"lc_amd.labels: the rows have different candidate counts {sorted(set(ks.tolist()))}, so there is no (B,K,3,4) "
+                         f"array of them; use symmetry_pose_candidates_list")
+    return out.view(len(ks), int(ks[0]) if len(ks) else 1, 3, 4)
+
+
 def _f32(name, t):
     """A contiguous float32 HIP tensor (16-bit and float64 inputs are converted; the labels take no gradient)."""
     return _lib.require_hip_f32(name, t.detach().float() if t.dtype == torch.float64 else t.detach())
@@ -94,11 +172,19 @@ def chunk_table(candis):
     return rows, ks, offs, r, o
 
 
-def _select(mode, candis, cam_K, N, *, pts_a=None, pts_b=None, xyz_map=None, noc_scale=None, homo_z=None, ck=None):
-    """One launch over every chunk: (Rt_best (B,3,4) f32, index within the row's candidates (B,) int32)."""
-    rows, ks, _, B, _ = chunk_table(candis)
+def _select(mode, candis, cam_K, N, *, pts_a=None, pts_b=None, xyz_map=None, noc_scale=None, homo_z=None, ck=None, table=None):
+    """One launch over every chunk: (Rt_best (B,3,4) f32, index within the row's candidates (B,) int32).  `table` = (SymmetrySet, base
+    poses (B,3,4) f32, obj_index (B,) int32) instead of `candis`: the candidates are formed in the launch."""
     dev = cam_K.device
-    cand = _f32("Rt_candi", torch.cat([c.reshape(-1, 3, 4) for c in candis], 0))
+    if table is None:
+        rows, ks, _, B, _ = chunk_table(candis)
+        cand = _f32("Rt_candi", torch.cat([c.reshape(-1, 3, 4) for c in candis], 0))
+    else:
+        symset, base, obj_index = table
+        B = int(base.shape[0])
+        if tuple(obj_index.shape) != (B,) or obj_index.dtype != torch.int32 or obj_index.device != base.device or base.device != symset.device:
+            raise ValueError(f"lc_amd.labels: obj_index must be ({B},) int32 on {symset.device}, like the base poses")
+        obj_index = obj_index.contiguous()
     K = _f32("cam_K", cam_K.reshape(B, 3, 3))
     Rt = torch.empty(B, 3, 4, device=dev, dtype=torch.float32)
     idx = torch.empty(B, device=dev, dtype=torch.int32)
@@ -120,11 +206,14 @@ def _select(mode, candis, cam_K, N, *, pts_a=None, pts_b=None, xyz_map=None, noc
             raise RuntimeError("lc_amd.labels: sym_ck_pts2d must be on the HIP device")
         ck = ck.to(torch.int64).contiguous()
     lib = _lib.load()
+    rest = (mode, _lib.ptr(K), _lib.ptr(pts_a), _lib.ptr(pts_b), _lib.ptr(xyz_map), code, bs, _lib.ptr(noc_scale), _lib.ptr(homo_z), _lib.ptr(ck), B, N, H, W,
+            _lib.ptr(Rt), _lib.ptr(idx), _lib.stream_ptr(dev))
     with _lib.on_device(dev):
-        rc = lib.lc_sym_select_f32(_lib.ptr(cand), _ints(rows), _ints(ks), len(ks), mode, _lib.ptr(K), _lib.ptr(pts_a), _lib.ptr(pts_b), _lib.ptr(xyz_map), code, bs,
-                                   _lib.ptr(noc_scale), _lib.ptr(homo_z), _lib.ptr(ck), B, N, H, W, _lib.ptr(Rt), _lib.ptr(idx),
-                                   _lib.stream_ptr(dev))
-    _lib.check(rc, "lc_sym_select_f32")
+        if table is None:
+            rc = lib.lc_sym_select_f32(_lib.ptr(cand), _ints(rows), _ints(ks), len(ks), *rest)
+        else:
+            rc = lib.lc_sym_select_table_f32(_lib.ptr(base), _lib.ptr(obj_index), *_table_args(symset), *rest)
+    _lib.check(rc, "lc_sym_select_f32" if table is None else "lc_sym_select_table_f32")
     return Rt, idx
 
 
@@ -202,11 +291,23 @@ def select_pose_3d(cam_K: Tensor, pts3d_out: Tensor, homo_z: Tensor, pose_candi:
 
 def _best(gt_dict, out_dict, sym_aware_started):
     """(Rt_best, the pose xyz_gt is computed with (B,3,4)) of `losses.py:68-118`."""
-    candis, homo_z, R_no_aug, t_no_aug, K_no_aug = itemgetter('Rt_candi', 'homo_z_out', 'R_no_aug', 't_no_aug', 'K_no_aug')(gt_dict)
-    if len(candis) == 1 and candis[0].shape[-3] == 1:  # no symmetric candidates: xyz_gt from the un-augmented pose (losses.py:72-76)
+    homo_z, R_no_aug, t_no_aug, K_no_aug = itemgetter('homo_z_out', 'R_no_aug', 't_no_aug', 'K_no_aug')(gt_dict)
+    table = None
+    if _SYM_SOURCE is not None:
+        # candidate 0 of every row is its base pose, and a row with one candidate keeps it: the reference's three paths (every row K = 1:
+        # xyz_gt from the un-augmented pose; not started: candidate 0; else the selection) need no knowledge of the batch's objects
+        Rt_base = torch.cat((R_no_aug.reshape(-1, 3, 3), t_no_aug.reshape(-1, 3, 1)), -1)
+        if not sym_aware_started or _SYM_SOURCE.max_k == 1:
+            return Rt_base, Rt_base
+        table = (_SYM_SOURCE, _base_pose(_SYM_SOURCE, R_no_aug, t_no_aug), _SYM_SOURCE.index_of(gt_dict['obj_id']))
+        candis, cand_dtype = None, R_no_aug.dtype
+    else:
+        candis = gt_dict['Rt_candi']
+        cand_dtype = candis[0].dtype
+    if table is None and len(candis) == 1 and candis[0].shape[-3] == 1:  # no symmetric candidates: xyz_gt from the un-augmented pose (losses.py:72-76)
         Rt_best = candis[0].squeeze(-3)
         return Rt_best, torch.cat((R_no_aug.reshape(-1, 3, 3), t_no_aug.reshape(-1, 3, 1)), -1)
-    if not sym_aware_started:
+    if table is None and not sym_aware_started:
         Rt_best = torch.cat([c[..., 0, :, :] for c in candis], 0)
         return Rt_best, Rt_best
     if 'pts2d' not in out_dict:
@@ -214,7 +315,7 @@ def _best(gt_dict, out_dict, sym_aware_started):
         B, N = int(ck.shape[0]), int(ck.shape[1])
         if 'xyz_noc' in out_dict:
             Rt, _ = _select(1, candis, K_no_aug, N, xyz_map=out_dict['xyz_noc'], noc_scale=_f32("noc_scale", gt_dict['noc_scale'].reshape(B, 3)),
-                            homo_z=homo_z, ck=ck)
+                            homo_z=homo_z, ck=ck, table=table)
         elif 'xyz_noc_bin' in out_dict:
             logits = out_dict['xyz_noc_bin'].detach()
             H, W = int(logits.shape[-2]), int(logits.shape[-1])
@@ -223,13 +324,13 @@ def _best(gt_dict, out_dict, sym_aware_started):
             pts = torch.empty(B, N, 3, device=logits.device, dtype=torch.float32)
             floatbits.decode_selected_rows(logits, gt_dict.get('bit_cnt', None), index, counts, pts, noc_scale=gt_dict['noc_scale'],
                                            model_transform=gt_dict.get('model_transform', None))
-            Rt, _ = _select(1, candis, K_no_aug, N, pts_a=pts, homo_z=homo_z, ck=ck)
+            Rt, _ = _select(1, candis, K_no_aug, N, pts_a=pts, homo_z=homo_z, ck=ck, table=table)
         else:
             raise RuntimeError('False branch')
     else:
         pts2d = out_dict['pts2d']
-        Rt, _ = _select(0, candis, gt_dict['out_K'], int(pts2d.shape[-2]), pts_a=_f32("pts3d", gt_dict['pts3d']), pts_b=_f32("pts2d", pts2d))
-    return Rt.to(candis[0].dtype), Rt
+        Rt, _ = _select(0, candis, gt_dict['out_K'], int(pts2d.shape[-2]), pts_a=_f32("pts3d", gt_dict['pts3d']), pts_b=_f32("pts2d", pts2d), table=table)
+    return Rt.to(cand_dtype), Rt
 
 
 def _pose_rep(Rt_best):
