@@ -7,6 +7,7 @@
     render   lc_amd/_C/liblc_amd_render.so   lc_amd/csrc/render/      include/lc_amd_render.h   the depth rasteriser
     crop     lc_amd/_C/liblc_amd_crop.so     lc_amd/csrc/crop/        include/lc_amd_crop.h     the zoom-in crops
     models   lc_amd/_C/liblc_amd_models.so   lc_amd/csrc/models/      include/lc_amd_models.h   model preparation (an offline tool's kernels)
+    symerr   lc_amd/_C/liblc_amd_symerr.so   lc_amd/csrc/symerr/      include/lc_amd_symerr.h   symmetry-aware pose errors (evaluation)
 
 A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`).
 Every function takes the library it works on as a `Target` (default: the hot-path library)."""
@@ -60,8 +61,11 @@ POSECOV = _side("posecov", (SHARED_H,))
 RENDER = _side("render")
 CROP = _side("crop")
 MODELS = _side("models", (SHARED_H,))  # the offline model preparation (lc_amd.models, python -m lc_amd.prep_models)
+# the evaluation side (lc_amd.metrics.compute_sym_pose_errors): its table rules are those of the label kernels, stated once in lc_sym_args.h
+SYMERR = _side("symerr", (SHARED_H, os.path.join(CSRC, "lc_sym_args.h")))
 _ALL = (MAIN, OPTIM, POSECOV, RENDER, CROP)
 _TOOLS = (MODELS,)
+_EVAL = (SYMERR,)
 HASH_MARKER = MAIN.hash_marker
 
 
@@ -74,6 +78,12 @@ def tool_targets():
     """The libraries behind the offline tools: built along with all_targets() by `python __graft_entry__.py build`, loaded by no training
     or test-time path."""
     return _TOOLS
+
+
+def eval_targets():
+    """The libraries behind the evaluation metrics that are no part of the training and test-time paths: built along with all_targets() by
+    `python __graft_entry__.py build`."""
+    return _EVAL
 
 
 def sources(target: Target = MAIN):
@@ -227,5 +237,5 @@ def build_variant(name: str, flags, verbose: bool = False) -> str:
 
 
 if __name__ == "__main__":
-    for t in all_targets() + tool_targets():
+    for t in all_targets() + tool_targets() + eval_targets():
         print(build(force=True, verbose=True, target=t))
