@@ -1,0 +1,240 @@
+"""GPU tests of VSD (lc_amd.vsd, lc_amd/csrc/vsd/lc_vsd.hip).  The score on the oracle's depth maps: every count equal to the numpy fp64
+oracle's (tests/vsd_oracle.py), every error the same bits.  The chain render -> score: bit for bit the score of what render_depth returns,
+and within the number of pixels the two renderers disagree on of the full numpy chain.  Windows, batch shapes, graph replay, B = 0.  The
+cases and the conditions that make exact equality a fair demand (tests/vsd_cases.py) are shown on the CPU by tests/test_vsd_oracle.py."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from tests import render_cases as rc
+from tests import render_oracle as ro
+from tests import vsd_cases as C
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+NAMES = [c.name for c in C.CASES]
+
+
+def _dev(a, rows=slice(None)):
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a[rows])).to(DEV)
+
+
+def _score(name, rows=slice(None), **kw):
+    from lc_amd import vsd
+
+    c, b = C.case(name), C.batch(name)
+    out = vsd.vsd_from_depth(_dev(b.depth_est, rows), _dev(b.depth_gt, rows), _dev(b.depth_test), _dev(b.K, rows), delta=C.DELTA, taus=c.taus,
+                             diameter=_dev(b.diameter, rows), scene_index=_dev(b.scene_index, rows), pixel_center=c.center, **kw)
+    return _np(out)
+
+
+def _np(out):
+    counts, errors = out.counts.cpu().numpy(), out.errors.cpu().numpy()
+    assert counts.dtype == np.int32 and errors.dtype == np.float32
+    return counts, errors
+
+
+def _same(got, want, what):
+    assert np.array_equal(got[0], want[0]), (what, "counts", got[0].tolist(), want[0].tolist())
+    assert np.array_equal(got[1].view(np.int32), want[1].view(np.int32)), (what, "errors")
+
+
+@functools.lru_cache(maxsize=None)
+def _meshes():
+    from lc_amd import render
+
+    return render.MeshSet([rc.MESHES[m] for m in C.MESH_NAMES], DEV)
+
+
+def _chain(name, rows=slice(None), **kw):
+    from lc_amd import vsd
+
+    c, b = C.case(name), C.batch(name)
+    return vsd.compute_vsd(_meshes(), _dev(b.mesh_index, rows), _dev(b.R_est, rows), _dev(b.t_est, rows), _dev(b.R_gt, rows), _dev(b.t_gt, rows),
+                           _dev(b.K, rows), _dev(b.depth_test), scene_index=_dev(b.scene_index, rows), delta=C.DELTA, taus=c.taus,
+                           diameter=_dev(b.diameter, rows), near=rc.NEAR, far=rc.FAR, pixel_center=c.center, **kw)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_score_equals_the_oracle(name):
+    """Counts entry for entry, errors bit for bit, refused rows -1 / NaN (a refused row's other arguments are those of a valid pose)."""
+    got, want = _score(name), C.expected(name)
+    refused = [i for i, r in enumerate(C.batch(name).refs) if r is None]
+    for i in refused:
+        assert (got[0][i] == -1).all() and np.isnan(got[1][i]).all(), i
+    _same(got, want, name)
+
+
+def test_scene_index_one_past_the_scenes_and_a_window_outside_the_frame():
+    from lc_amd import vsd
+
+    name = C.WINDOW_CASE
+    c, b = C.case(name), C.batch(name)
+    h, w = C.WINDOW_HW
+    H, W = c.size_hw
+    origins = np.array([[0, 0], [W - w, H - h], [W - w + 1, 0], [-1, 3]], dtype=np.int32)  # rows 2 and 3 reach outside: refused
+
+    def crops(maps):  # a refused row's maps are never read: zeros of the right shape
+        return np.stack([maps[i, y:y + h, x:x + w] if 0 <= x <= W - w and 0 <= y <= H - h else np.zeros((h, w), np.float32)
+                         for i, (x, y) in enumerate(origins)])
+
+    est, gt = crops(b.depth_est), crops(b.depth_gt)
+    scene = np.array([0, len(c.scenes), 0, 0], dtype=np.int32)  # row 1: one past the scenes
+    out = vsd.vsd_from_depth(_dev(est), _dev(gt), _dev(b.depth_test), _dev(b.K), delta=C.DELTA, taus=c.taus, diameter=_dev(b.diameter),
+                             scene_index=_dev(scene), window_xy=_dev(origins))
+    counts, errors = _np(out)
+    for i in (1, 2, 3):
+        assert (counts[i] == -1).all() and np.isnan(errors[i]).all(), i
+    from tests import vsd_oracle
+
+    ref = vsd_oracle.score(est[0], gt[0], b.depth_test[0], c.K, C.DELTA, c.taus, b.diameter[0], (0, 0))
+    assert np.array_equal(counts[0], ref.counts) and np.array_equal(errors[0].view(np.int32), ref.errors.view(np.int32))
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_chain_is_render_then_score_and_close_to_the_numpy_chain(name):
+    from lc_amd import render, vsd
+
+    c, b = C.case(name), C.batch(name)
+    B = len(c.rows)
+    got = _chain(name)
+    idx, K = _dev(b.mesh_index), _dev(b.K)
+    r = render.render_depth(_meshes(), torch.cat((idx, idx)), torch.cat((_dev(b.R_est), _dev(b.R_gt))), torch.cat((_dev(b.t_est), _dev(b.t_gt))),
+                            torch.cat((K, K)), c.size_hw, near=rc.NEAR, far=rc.FAR, pixel_center=c.center)
+    two = vsd.vsd_from_depth(r.depth[:B], r.depth[B:], _dev(b.depth_test), K, delta=C.DELTA, taus=c.taus, diameter=_dev(b.diameter),
+                             scene_index=_dev(b.scene_index), pixel_center=c.center)
+    _same(_np(got), _np(two), name)
+    assert got.info.shape == (B, 2) and torch.equal(got.info, torch.stack((r.info[:B], r.info[B:]), -1)) and not got.info.any()
+    # against render oracle -> score oracle: a count can differ by the pixels on which the two renderers may differ
+    counts = got.counts.cpu().numpy()
+    d_est, d_gt = r.depth[:B].cpu().numpy(), r.depth[B:].cpu().numpy()
+    for i, ref in enumerate(b.refs):
+        if ref is None:
+            assert (counts[i] == -1).all()
+            continue
+        differ = int(((d_est[i] != b.depth_est[i]) | (d_gt[i] != b.depth_gt[i])).sum())
+        bound = int(b.ties[i]) + differ
+        worst = int(np.abs(counts[i].astype(np.int64) - ref.counts).max())
+        print(f"{name} row {i}: {differ} pixels differ between the renderers, {int(b.ties[i])} tie pixels, largest count difference {worst}")
+        assert worst <= bound
+
+
+def test_unknown_mesh_is_refused():
+    from lc_amd import vsd
+
+    name = "ico-depths-64x64"
+    c, b = C.case(name), C.batch(name)
+    idx = b.mesh_index.copy()
+    idx[1], idx[2] = -1, len(C.MESH_NAMES)
+    out = vsd.compute_vsd(_meshes(), _dev(idx), _dev(b.R_est), _dev(b.t_est), _dev(b.R_gt), _dev(b.t_gt), _dev(b.K), _dev(b.depth_test),
+                          scene_index=_dev(b.scene_index), delta=C.DELTA, taus=c.taus, diameter=_dev(b.diameter), near=rc.NEAR, far=rc.FAR)
+    counts, errors = _np(out)
+    info = out.info.cpu().numpy()
+    for i in (1, 2):
+        assert (counts[i] == -1).all() and np.isnan(errors[i]).all() and (info[i] == -1).all(), i
+    ok = [0, 3, 4]
+    want = _np(_chain(name))
+    _same((counts[ok], errors[ok]), (want[0][ok], want[1][ok]), "the other rows")
+    assert not info[ok].any() and (counts[5] == -1).all()
+
+
+def test_windows():
+    """An integer-valued principal point, so the fp32 shift of K is exact and a window's render is the frame's render cropped."""
+    from lc_amd import vsd
+
+    name = C.WINDOW_CASE
+    c, b = C.case(name), C.batch(name)
+    rows = [0, 1, 2]
+    full = _np(_chain(name, rows))
+    h, w = C.WINDOW_HW
+    boxes = [C.silhouette_box(name, [i]) for i in rows]
+    assert all(x1 - x0 + 1 <= w - 4 and y1 - y0 + 1 <= h - 2 for x0, y0, x1, y1 in boxes)
+    H, W = c.size_hw
+    inside = np.array([[min(max(x0 - 1 - i, 0), W - w), min(max(y0 - 1, 0), H - h)] for i, (x0, y0, x1, y1) in enumerate(boxes)], dtype=np.int32)
+    assert len({int(x) % 4 for x, _ in inside}) > 1  # origins of more than one phase: rows that take the 16-byte loads and rows that cannot
+    got = _np(_chain(name, rows, window_hw=(h, w), window_xy=_dev(inside)))
+    _same(got, full, "windows that hold both silhouettes")
+    assert not got[0][:, 2].any()
+    cut = inside.copy()
+    cut[0, 0] = min((boxes[0][0] + boxes[0][2]) // 2, W - w)  # the left side through the ico
+    assert boxes[0][0] < cut[0, 0] <= boxes[0][2]
+    cut[1, 1] = (boxes[1][1] + boxes[1][3]) // 2 - h  # the bottom side through the torus
+    assert cut[1, 1] >= 0
+    got = _np(_chain(name, rows, window_hw=(h, w), window_xy=_dev(cut)))
+    assert got[0][0, 2] > 0 and got[0][1, 2] > 0 and got[0][2, 2] == 0
+    assert got[0][0, 0] < full[0][0, 0] and np.array_equal(got[0][2], full[0][2])
+    # window_origins puts such a window around the pair by itself
+    auto = vsd.window_origins(_dev(b.t_est, rows), _dev(b.t_gt, rows), _dev(b.K, rows), _dev(b.diameter, rows), (h, w), c.size_hw)
+    assert auto.dtype == torch.int32 and auto.is_cuda
+    _same(_np(_chain(name, rows, window_hw=(h, w), window_xy=auto)), full, "window_origins")
+
+
+def test_same_bits_in_every_batch_shape():
+    for name in ("occlusion-stress-33x47", "torus-t16-20x45"):
+        B = len(C.case(name).rows)
+        together = _score(name)
+        one_by_one = [_score(name, slice(i, i + 1)) for i in range(B)]
+        _same((np.concatenate([a for a, _ in one_by_one]), np.concatenate([e for _, e in one_by_one])), together, (name, "one by one"))
+        rev = _score(name, slice(None, None, -1))
+        _same((rev[0][::-1], rev[1][::-1]), together, (name, "reversed"))
+        # the same rows one element further into their allocations: every 16-byte phase moves
+        from lc_amd import vsd
+
+        c, b = C.case(name), C.batch(name)
+
+        def shifted(a):
+            t = _dev(a)
+            buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=DEV)
+            buf[1:].copy_(t.reshape(-1))
+            return buf[1:].view(t.shape)
+
+        out = vsd.vsd_from_depth(shifted(b.depth_est), _dev(b.depth_gt), shifted(b.depth_test), _dev(b.K), delta=C.DELTA, taus=c.taus,
+                                 diameter=_dev(b.diameter), scene_index=_dev(b.scene_index))
+        _same(_np(out), together, (name, "shifted"))
+
+
+def test_graph_replay():
+    name = "ico-depths-64x64"
+    b = C.batch(name)
+    t = {k: _dev(getattr(b, k)) for k in ("mesh_index", "R_est", "t_est", "R_gt", "t_gt", "K", "depth_test", "scene_index", "diameter")}
+
+    def call():
+        from lc_amd import vsd
+
+        return vsd.compute_vsd(_meshes(), t["mesh_index"], t["R_est"], t["t_est"], t["R_gt"], t["t_gt"], t["K"], t["depth_test"],
+                               scene_index=t["scene_index"], delta=C.DELTA, taus=C.case(name).taus, diameter=t["diameter"], near=rc.NEAR, far=rc.FAR)
+
+    eager = _np(call())  # the warm call
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        call()
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):  # a host synchronisation or a read-back in here would fail the capture
+        assert torch.cuda.is_current_stream_capturing()
+        out = call()
+    assert not torch.cuda.is_current_stream_capturing()
+    perm = [4, 2, 0, 5, 1, 3]  # new poses written into the same tensors
+    for k in ("R_est", "t_est", "scene_index"):
+        t[k].copy_(_dev(getattr(b, k))[perm])
+    for _ in range(2):
+        g.replay()
+        torch.cuda.synchronize()
+        _same(_np(out), (eager[0][perm], eager[1][perm]), "replay")
+    _same(_np(call()), (eager[0][perm], eager[1][perm]), "eager after the copy")
+
+
+def test_empty_batch():
+    from lc_amd import vsd
+
+    name = "ico-depths-64x64"
+    c, b = C.case(name), C.batch(name)
+    out = vsd.vsd_from_depth(_dev(b.depth_est)[:0], _dev(b.depth_gt)[:0], _dev(b.depth_test), _dev(b.K)[:0], delta=C.DELTA, taus=c.taus,
+                             scene_index=_dev(b.scene_index)[:0])
+    assert out.counts.shape == (0, 13) and out.errors.shape == (0, 10) and out.counts.dtype == torch.int32
+    out = _chain(name, slice(0, 0))
+    assert out.counts.shape == (0, 13) and out.errors.shape == (0, 10) and out.info.shape == (0, 2)
