@@ -9,6 +9,7 @@
     models   lc_amd/_C/liblc_amd_models.so   lc_amd/csrc/models/      include/lc_amd_models.h   model preparation (an offline tool's kernels)
     symerr   lc_amd/_C/liblc_amd_symerr.so   lc_amd/csrc/symerr/      include/lc_amd_symerr.h   symmetry-aware pose errors (evaluation)
     vsd      lc_amd/_C/liblc_amd_vsd.so      lc_amd/csrc/vsd/         include/lc_amd_vsd.h      BOP's VSD from rendered and scene depth (evaluation)
+    gtinfo   lc_amd/_C/liblc_amd_gtinfo.so   lc_amd/csrc/gtinfo/      include/lc_amd_gtinfo.h   BOP's ground-truth visibility annotations (an offline tool's kernels)
 
 A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`).
 Every function takes the library it works on as a `Target` (default: the hot-path library)."""
@@ -65,10 +66,13 @@ MODELS = _side("models", (SHARED_H,))  # the offline model preparation (lc_amd.m
 # the evaluation side (lc_amd.metrics.compute_sym_pose_errors): its table rules are those of the label kernels, stated once in lc_sym_args.h
 SYMERR = _side("symerr", (SHARED_H, os.path.join(CSRC, "lc_sym_args.h")))
 VSD = _side("vsd")  # the evaluation error that reads the scene's depth (lc_amd.vsd); includes nothing from outside its directory but its header
+# the annotation side (lc_amd.gtinfo, python -m lc_amd.gen_gt_info); restates the ray length of VSD and includes nothing but its own header
+GTINFO = _side("gtinfo")
 _ALL = (MAIN, OPTIM, POSECOV, RENDER, CROP)
 _TOOLS = (MODELS,)
 _EVAL = (SYMERR,)
 _SCENE = (VSD,)
+_ANNOT = (GTINFO,)
 HASH_MARKER = MAIN.hash_marker
 
 
@@ -93,6 +97,12 @@ def scene_targets():
     """The libraries behind the evaluation metrics that read the scene's measured depth: built along with all_targets() by
     `python __graft_entry__.py build`."""
     return _SCENE
+
+
+def annot_targets():
+    """The libraries behind the dataset annotations (visibility records, composed scene depth): built along with all_targets() by
+    `python __graft_entry__.py build`, loaded by no training or test-time path."""
+    return _ANNOT
 
 
 def sources(target: Target = MAIN):
@@ -246,5 +256,5 @@ def build_variant(name: str, flags, verbose: bool = False) -> str:
 
 
 if __name__ == "__main__":
-    for t in all_targets() + tool_targets() + eval_targets() + scene_targets():
+    for t in all_targets() + tool_targets() + eval_targets() + scene_targets() + annot_targets():
         print(build(force=True, verbose=True, target=t))
