@@ -10,6 +10,7 @@
     symerr   lc_amd/_C/liblc_amd_symerr.so   lc_amd/csrc/symerr/      include/lc_amd_symerr.h   symmetry-aware pose errors (evaluation)
     vsd      lc_amd/_C/liblc_amd_vsd.so      lc_amd/csrc/vsd/         include/lc_amd_vsd.h      BOP's VSD from rendered and scene depth (evaluation)
     gtinfo   lc_amd/_C/liblc_amd_gtinfo.so   lc_amd/csrc/gtinfo/      include/lc_amd_gtinfo.h   BOP's ground-truth visibility annotations (an offline tool's kernels)
+    maskcrop lc_amd/_C/liblc_amd_maskcrop.so lc_amd/csrc/maskcrop/    include/lc_amd_maskcrop.h the training mask crops: warps, valid count, check points
 
 A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`).
 Every function takes the library it works on as a `Target` (default: the hot-path library)."""
@@ -68,11 +69,14 @@ SYMERR = _side("symerr", (SHARED_H, os.path.join(CSRC, "lc_sym_args.h")))
 VSD = _side("vsd")  # the evaluation error that reads the scene's depth (lc_amd.vsd); includes nothing from outside its directory but its header
 # the annotation side (lc_amd.gtinfo, python -m lc_amd.gen_gt_info); restates the ray length of VSD and includes nothing but its own header
 GTINFO = _side("gtinfo")
+# the loader side of training (lc_amd.maskcrop); restates the coordinates of CROP and includes nothing but its own header
+MASKCROP = _side("maskcrop")
 _ALL = (MAIN, OPTIM, POSECOV, RENDER, CROP)
 _TOOLS = (MODELS,)
 _EVAL = (SYMERR,)
 _SCENE = (VSD,)
 _ANNOT = (GTINFO,)
+_LOADER = (MASKCROP,)
 HASH_MARKER = MAIN.hash_marker
 
 
@@ -103,6 +107,12 @@ def annot_targets():
     """The libraries behind the dataset annotations (visibility records, composed scene depth): built along with all_targets() by
     `python __graft_entry__.py build`, loaded by no training or test-time path."""
     return _ANNOT
+
+
+def loader_targets():
+    """The libraries behind the training loader's per-instance work that is no part of the per-step paths: built along with all_targets() by
+    `python __graft_entry__.py build`."""
+    return _LOADER
 
 
 def sources(target: Target = MAIN):
@@ -256,5 +266,5 @@ def build_variant(name: str, flags, verbose: bool = False) -> str:
 
 
 if __name__ == "__main__":
-    for t in all_targets() + tool_targets() + eval_targets() + scene_targets() + annot_targets():
+    for t in all_targets() + tool_targets() + eval_targets() + scene_targets() + annot_targets() + loader_targets():
         print(build(force=True, verbose=True, target=t))

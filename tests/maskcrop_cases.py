@@ -1,0 +1,89 @@
+"""The case list of the training mask crops, shared by tests/test_maskcrop_oracle.py (numpy) and tests/test_gpu_maskcrop.py (device):
+small windows of 5 x 7 up to 48 x 40, matrices from the identity to the stretched and skewed kind of the suite's `stress` camera, origins
+on both sides of zero, crops that straddle each window edge or miss the window.  The crop sizes follow the warp launch's shape: a
+workgroup covers a band of 16 crop rows (more where the crop is narrower than 64), its 256 threads laid out as 16 x 16 quads of four
+pixels at w = 64, so 16 x 64 is one pass of one workgroup exactly; a row more starts a second band, a column more a second quad layout
+(32 x 8) with a partial quad."""
+import math
+from typing import NamedTuple
+
+import numpy as np
+
+TILE_H, TILE_W = 16, 64
+EYE = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0))
+
+
+class Warp(NamedTuple):
+    name: str
+    mask_hw: tuple
+    seed: int
+    origin: tuple  # (x0, y0)
+    M: tuple       # (2,3), frame -> crop
+    out_hw: tuple
+
+
+def mask(hw, seed):
+    """A (Hm,Wm) uint8 0/1 window; seed < 0: all set (the window's edges alone decide)."""
+    if seed < 0:
+        return np.ones(hw, dtype=np.uint8)
+    return (np.random.default_rng(seed).random(hw) < 0.6).astype(np.uint8)
+
+
+def noc_with(valid, hw, seed):
+    """A (h,w) uint8 mask with exactly `valid` set pixels, anywhere."""
+    m = np.zeros(hw[0] * hw[1], dtype=np.uint8)
+    m[np.random.default_rng(seed).permutation(m.size)[:valid]] = 1
+    return m.reshape(hw)
+
+
+def embed(window, origin):
+    """(frame, (dx, dy)): a frame that holds the window at its origin, so that frame pixel (X + dx, Y + dy) is the contract's frame pixel
+    (X, Y).  A non-negative origin gives the frame itself (dx = dy = 0); else the window serves, shifted."""
+    x0, y0 = int(origin[0]), int(origin[1])
+    if x0 >= 0 and y0 >= 0:
+        frame = np.zeros((y0 + window.shape[0], x0 + window.shape[1]), dtype=np.uint8)
+        frame[y0:, x0:] = window
+        return frame, (0, 0)
+    return window, (-x0, -y0)
+
+
+def affine(center, zoom, out_hw, rot=0.0, stretch=1.0, skew=0.0, shift=(0.0, 0.0)):
+    """Forward matrix that takes frame point `center` to the crop's centre (+ shift): rotation by rot, zoom (crop pixels per frame pixel),
+    x stretched by `stretch`, x sheared by `skew` of y."""
+    c, s = math.cos(rot), math.sin(rot)
+    A = np.array([[c, s], [-s, c]]) @ np.array([[stretch, skew], [0.0, 1.0]]) * zoom
+    t = np.array([out_hw[1] * 0.5 + shift[0], out_hw[0] * 0.5 + shift[1]]) - A @ np.asarray(center, dtype=np.float64)
+    return tuple(map(tuple, np.concatenate((A, t[:, None]), 1).astype(np.float32).tolist()))
+
+
+def _centre(mask_hw, origin):
+    return (origin[0] + mask_hw[1] * 0.5, origin[1] + mask_hw[0] * 0.5)
+
+
+def _warps():
+    out = []
+
+    def add(name, mask_hw, seed, origin, out_hw, M=None, **kw):
+        out.append(Warp(name, mask_hw, seed, origin, M if M is not None else affine(_centre(mask_hw, origin), out_hw=out_hw, **kw), out_hw))
+
+    add("identity-5x7", (5, 7), 1, (0, 0), (5, 7), M=EYE)
+    add("identity-1x1", (5, 7), 2, (0, 0), (1, 1), M=((1.0, 0.0, -3.0), (0.0, 1.0, -2.0)))
+    add("shift-fraction-1x37", (9, 40), 3, (0, 0), (1, 37), M=((1.0, 0.0, -0.3125), (0.0, 1.0, -3.71875)))
+    add("shift-fraction-37x1", (40, 9), 4, (0, 0), (37, 1), M=((1.0, 0.0, -4.4), (0.0, 1.0, 0.53)))
+    add("rot30-one-tile", (48, 40), 5, (3, 2), (TILE_H, TILE_W), zoom=1.4, rot=math.radians(30))
+    add("rot90-tile-plus-row", (31, 33), 6, (0, 0), (TILE_H + 1, TILE_W), zoom=1.0, rot=math.pi / 2)
+    add("rot200-tile-plus-col", (40, 48), 7, (-5, 4), (TILE_H, TILE_W + 1), zoom=1.7, rot=math.radians(200))
+    add("zoom-in-3x-64", (20, 24), 8, (10, -7), (64, 64), zoom=3.0)
+    add("zoom-out-3x-64", (48, 40), 9, (-11, -13), (64, 64), zoom=1.0 / 3.0)
+    add("stress-64", (33, 47), 10, (6, 9), (64, 64), zoom=1.6, rot=math.radians(17), stretch=1.31, skew=0.23)
+    add("stress-odd", (48, 40), 11, (-20, 15), (23, 41), zoom=0.9, rot=math.radians(-71), stretch=0.77, skew=-0.4)
+    # all-set windows: the values are decided by the window's edges alone
+    add("edge-left", (12, 14), -1, (5, 5), (18, 19), zoom=1.3, shift=(6.3, 0.0))
+    add("edge-right", (12, 14), -1, (5, 5), (18, 19), zoom=1.3, shift=(-6.7, 0.0))
+    add("edge-top", (12, 14), -1, (-30, -40), (18, 19), zoom=1.3, shift=(0.0, 5.9), rot=0.1)
+    add("edge-bottom", (12, 14), -1, (-30, -40), (18, 19), zoom=1.3, shift=(0.0, -6.1), rot=-0.1)
+    add("window-outside", (12, 14), -1, (200, 300), (18, 19), M=EYE)
+    return tuple(out)
+
+
+WARPS = _warps()
