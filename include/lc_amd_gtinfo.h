@@ -17,7 +17,7 @@
  * Window pixel (x,y) is frame pixel (X,Y) = (x + x0, y + y0).  obj = d_gt > 0.  Where (X,Y) lies in the frame (0 <= X < W, 0 <= Y < H):
  *   1. ray length, fp64 on the exactly widened fp32 inputs, every product, sum, quotient and root rounded on its own (no fused
  *      multiply-add):  px = X + pcx - K02,  py = Y + pcy - K12,  Yk = py / K11,  Xk = (px - K01 Yk) / K00,
- *      n = sqrt(Xk Xk + Yk Yk + 1) with the sum taken as (Xk Xk + Yk Yk) + 1  (steps 1 and 2 of lc_amd_vsd.h, restated here)
+ *      n = sqrt(Xk Xk + Yk Yk + 1) with the sum taken as (Xk Xk + Yk Yk) + 1  (steps 1 and 2 of lc_amd_vsd.h; one copy on the device, csrc/shared/lc_ray_length.h)
  *   2. valid = obj and d_test > 0
  *      visib = obj and (test missing or d_gt n - d_test n <= delta), the two products and the difference formed in fp64
  * Outside the frame a pixel is obj at most: neither valid nor visible, and nothing of depth_test is read for it.

@@ -14,7 +14,7 @@
  *   h, w: the crop;  vis_interp: LC_MASKCROP_NEAREST or LC_MASKCROP_LINEAR;  valid_th, n_check (0: no check points; at most
  *      LC_MASKCROP_MAX_CHECK);  seed (uint64, by value);  sample_id (B) int32 or NULL (row b is sample b)
  *
- * Coordinates: exactly those of lc_amd_crop.h, restated.  M widened to fp64, every product and sum rounded on its own:
+ * Coordinates: exactly those of lc_amd_crop.h (one copy on the device, csrc/shared/lc_warp_grid.h).  M widened to fp64, every product and sum rounded on its own:
  *     D = M00 M11 - M01 M10;  D = D != 0 ? 1 / D : 0
  *     m00 = M11 D   m01 = -M01 D   m10 = -M10 D   m11 = M00 D      b1 = -m00 M02 - m01 M12      b2 = -m10 M02 - m11 M12
  *   crop pixel (x, y); rint is round-half-even, every rint result is clamped to +-2^30, the sums are 64-bit:

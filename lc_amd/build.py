@@ -12,7 +12,9 @@
     gtinfo   lc_amd/_C/liblc_amd_gtinfo.so   lc_amd/csrc/gtinfo/      include/lc_amd_gtinfo.h   BOP's ground-truth visibility annotations (an offline tool's kernels)
     maskcrop lc_amd/_C/liblc_amd_maskcrop.so lc_amd/csrc/maskcrop/    include/lc_amd_maskcrop.h the training mask crops: warps, valid count, check points
 
-A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`).
+A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`): code that
+two libraries need exists once there (lc_shared.h: main, posecov, models, symerr; lc_warp_grid.h: crop, maskcrop; lc_ray_length.h: vsd,
+gtinfo; lc_wave_int.h: vsd, gtinfo, maskcrop), and no side library restates another's arithmetic.
 Every function takes the library it works on as a `Target` (default: the hot-path library)."""
 from __future__ import annotations
 
@@ -50,6 +52,9 @@ class Target(NamedTuple):
 
 SHARED = os.path.join(CSRC, "shared")
 SHARED_H = os.path.join(SHARED, "lc_shared.h")  # the fp64 cross-lane layer: the order-defining reductions of MAIN and POSECOV
+WARP_GRID_H = os.path.join(SHARED, "lc_warp_grid.h")  # the fixed-point warp coordinates and launch geometry of CROP and MASKCROP
+RAY_LENGTH_H = os.path.join(SHARED, "lc_ray_length.h")  # the ray length through a pixel and the phase-aligned group loads of VSD and GTINFO
+WAVE_INT_H = os.path.join(SHARED, "lc_wave_int.h")  # the integer wave butterflies of VSD, GTINFO and MASKCROP
 
 
 def _side(name: str, shared: tuple = ()) -> Target:
@@ -62,15 +67,15 @@ MAIN = Target("main", CSRC, "lc_amd.h", SO_PATH, b"LC_AMD_SRC_HASH:", (SHARED_H,
 OPTIM = _side("optim")
 POSECOV = _side("posecov", (SHARED_H,))
 RENDER = _side("render")
-CROP = _side("crop")
+CROP = _side("crop", (WARP_GRID_H,))
 MODELS = _side("models", (SHARED_H,))  # the offline model preparation (lc_amd.models, python -m lc_amd.prep_models)
 # the evaluation side (lc_amd.metrics.compute_sym_pose_errors): its table rules are those of the label kernels, stated once in lc_sym_args.h
 SYMERR = _side("symerr", (SHARED_H, os.path.join(CSRC, "lc_sym_args.h")))
-VSD = _side("vsd")  # the evaluation error that reads the scene's depth (lc_amd.vsd); includes nothing from outside its directory but its header
-# the annotation side (lc_amd.gtinfo, python -m lc_amd.gen_gt_info); restates the ray length of VSD and includes nothing but its own header
-GTINFO = _side("gtinfo")
-# the loader side of training (lc_amd.maskcrop); restates the coordinates of CROP and includes nothing but its own header
-MASKCROP = _side("maskcrop")
+VSD = _side("vsd", (RAY_LENGTH_H, WAVE_INT_H))  # the evaluation error that reads the scene's depth (lc_amd.vsd)
+# the annotation side (lc_amd.gtinfo, python -m lc_amd.gen_gt_info); shares the ray length with VSD
+GTINFO = _side("gtinfo", (RAY_LENGTH_H, WAVE_INT_H))
+# the loader side of training (lc_amd.maskcrop); shares the coordinates with CROP
+MASKCROP = _side("maskcrop", (WARP_GRID_H, WAVE_INT_H))
 _ALL = (MAIN, OPTIM, POSECOV, RENDER, CROP)
 _TOOLS = (MODELS,)
 _EVAL = (SYMERR,)
@@ -113,6 +118,11 @@ def loader_targets():
     """The libraries behind the training loader's per-instance work that is no part of the per-step paths: built along with all_targets() by
     `python __graft_entry__.py build`."""
     return _LOADER
+
+
+def every_target():
+    """Every library, the six groups in build order."""
+    return all_targets() + tool_targets() + eval_targets() + scene_targets() + annot_targets() + loader_targets()
 
 
 def sources(target: Target = MAIN):
@@ -266,5 +276,5 @@ def build_variant(name: str, flags, verbose: bool = False) -> str:
 
 
 if __name__ == "__main__":
-    for t in all_targets() + tool_targets() + eval_targets() + scene_targets() + annot_targets() + loader_targets():
+    for t in every_target():
         print(build(force=True, verbose=True, target=t))

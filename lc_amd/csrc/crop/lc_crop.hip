@@ -4,7 +4,7 @@
 // What the reference's loader does per instance on the host with cv2.warpAffine (dataset.py:409-411, 425-426) followed by
 // `.to(float32).div(255)` and transforms.Normalize (test.py:163): here every crop of a batch is cut from frames that were uploaded
 // once, in OpenCV's published fixed-point scheme for 8-bit images (coordinates on a 1/1024 px grid, bilinear weights on a 1/32 px
-// grid), which is pure integer arithmetic after the inverse matrix.
+// grid), which is pure integer arithmetic after the inverse matrix (shared/lc_warp_grid.h, with the training mask crops).
 //
 //   one workgroup of four waves per (row, band of crop rows).  Thread 0 forms the row's inverse matrix in fp64 and judges the row;
 //   all threads fill a 256 C-entry table of the FINISHED output values in LDS (there are only 256 values per channel, so the
@@ -13,19 +13,15 @@
 //   and one store of four pixels per channel plane (16 bytes for fp32, 8 for the 16-bit types, 4 for uint8; element by element
 //   where w is no multiple of four or the output is not aligned).
 //
-// The coordinate arithmetic is written with __dmul_rn / __dadd_rn: the library is built with -ffp-contract=on, and m01 * y + b1 in one
-// expression would be fused and can move X by one.
-//
 // Bounds: every tap is range-checked against the frame on its own (that IS the border rule), a bad row sees a frame of size zero, and
 // the frame index is checked before it is used, so that no input value can make the launch read or write outside its arrays.
-//
-// Self-contained on purpose: the library's source hash covers this directory and its header only.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <string>
 
 #include "../../../include/lc_amd_crop.h"
+#include "../shared/lc_warp_grid.h"
 
 #ifndef LC_AMD_CROP_SRC_HASH
 #define LC_AMD_CROP_SRC_HASH "unrecorded"
@@ -42,9 +38,7 @@ int fail(int code, std::string msg) {
 }
 
 constexpr int kThreads = 256;
-constexpr int kMinBand = 16;           // crop rows per workgroup (more where a pass of the workgroup covers more)
-constexpr double kAbScale = 1024.0;    // 1 << AB_BITS
-constexpr double kFixLimit = 1073741824.0;  // 2^30
+constexpr int kMinBand = 16;  // crop rows per workgroup (more where a pass of the workgroup covers more)
 
 struct Params {
     const unsigned char* frames;
@@ -53,8 +47,7 @@ struct Params {
     void* out;
     int* info;
     int F, H, W, B, h, w;
-    int band, nbands;  // crop rows per workgroup, workgroups per row of the batch
-    int lg_tx;         // log2 of the threads along x
+    lc::WarpGrid grid;
     int vec;           // four-pixel stores are possible (w % 4 == 0 and the output is aligned to them)
     int normalize;
     float mean[3], std[3];
@@ -90,11 +83,6 @@ __device__ inline typename Store<DT>::type finish(int v, int c, const Params& p)
     }
 }
 
-// rint (half to even), clamped to +-2^30, as an integer.  fmax / fmin also turn a NaN into a bound.
-__device__ inline int fix(double v) {
-    return (int)fmin(fmax(rint(v), -kFixLimit), kFixLimit);
-}
-
 template <int DT, int C, bool LINEAR>
 __global__ __launch_bounds__(kThreads) void lc_crop_warp_kernel(const Params p) {
     using T = typename Store<DT>::type;
@@ -104,26 +92,11 @@ __global__ __launch_bounds__(kThreads) void lc_crop_warp_kernel(const Params p) 
     __shared__ int s_frame;  // -1 = bad row
 
     const int tid = threadIdx.x;
-    const int b = blockIdx.x / p.nbands, band = blockIdx.x - b * p.nbands;
+    const int b = blockIdx.x / p.grid.nbands, band = blockIdx.x - b * p.grid.nbands;
     if (tid == 0) {
         const int f = p.frame_index ? p.frame_index[b] : b;
         bool ok = f >= 0 && f < p.F;
-        double M[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            const float m = p.M[6 * (size_t)b + k];
-            ok = ok && (__float_as_uint(m) & 0x7f800000u) != 0x7f800000u;
-            M[k] = (double)m;
-        }
-        double D = __dadd_rn(__dmul_rn(M[0], M[4]), -__dmul_rn(M[1], M[3]));
-        D = D != 0.0 ? 1.0 / D : 0.0;
-        const double m00 = __dmul_rn(M[4], D), m01 = __dmul_rn(-M[1], D), m10 = __dmul_rn(-M[3], D), m11 = __dmul_rn(M[0], D);
-        s_inv[0] = m00;
-        s_inv[1] = m01;
-        s_inv[2] = __dadd_rn(__dmul_rn(-m00, M[2]), -__dmul_rn(m01, M[5]));
-        s_inv[3] = m10;
-        s_inv[4] = m11;
-        s_inv[5] = __dadd_rn(__dmul_rn(-m10, M[2]), -__dmul_rn(m11, M[5]));
+        ok = lc::inverse_of(p.M + 6 * (size_t)b, ok, s_inv);
         s_frame = ok ? f : -1;
         if (band == 0 && p.info) p.info[b] = ok ? 0 : -1;
     }
@@ -139,11 +112,11 @@ __global__ __launch_bounds__(kThreads) void lc_crop_warp_kernel(const Params p) 
     T* out = static_cast<T*>(p.out) + (size_t)b * C * p.h * p.w;
     const size_t plane = (size_t)p.h * p.w;
 
-    const int TX = 1 << p.lg_tx, TY = kThreads >> p.lg_tx;
-    const int tx = tid & (TX - 1), ty = tid >> p.lg_tx;
+    const int TX = 1 << p.grid.lg_tx, TY = kThreads >> p.grid.lg_tx;
+    const int tx = tid & (TX - 1), ty = tid >> p.grid.lg_tx;
     const int quads = (p.w + 3) >> 2;
-    const int y_end = min(p.h, (band + 1) * p.band);
-    constexpr long long kDelta = LINEAR ? 16 : 512;
+    const int y_end = min(p.h, (band + 1) * p.grid.band);
+    constexpr long long kDelta = LINEAR ? lc::kLinearDelta : lc::kNearestDelta;
 
     auto tap = [&](int xx, int yy, int (&s)[C]) {
         const bool in = (unsigned)xx < (unsigned)W && (unsigned)yy < (unsigned)H;
@@ -155,24 +128,16 @@ __global__ __launch_bounds__(kThreads) void lc_crop_warp_kernel(const Params p) 
     for (int xq = tx; xq < quads; xq += TX) {
         const int x0 = xq << 2;
         int ax[4], ay[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const double x = (double)(x0 + j);
-            ax[j] = fix(__dmul_rn(__dmul_rn(m00, x), kAbScale));
-            ay[j] = fix(__dmul_rn(__dmul_rn(m10, x), kAbScale));
-        }
-        for (int y = band * p.band + ty; y < y_end; y += TY) {
-            const double yd = (double)y;
-            const long long X0 = (long long)fix(__dmul_rn(__dadd_rn(__dmul_rn(m01, yd), b1), kAbScale)) + kDelta;
-            const long long Y0 = (long long)fix(__dmul_rn(__dadd_rn(__dmul_rn(m11, yd), b2), kAbScale)) + kDelta;
+        lc::quad_terms(m00, m10, x0, ax, ay);
+        for (int y = band * p.grid.band + ty; y < y_end; y += TY) {
+            const long long X0 = lc::row_term(m01, b1, y) + kDelta, Y0 = lc::row_term(m11, b2, y) + kDelta;
             Vec4<T> res[C];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const long long X = X0 + ax[j], Y = Y0 + ay[j];
                 int v[C];
                 if constexpr (LINEAR) {
-                    const int Xs = (int)(X >> 5), Ys = (int)(Y >> 5);
-                    const int sx = Xs >> 5, sy = Ys >> 5, fx = Xs & 31, fy = Ys & 31;
+                    const auto [sx, sy, fx, fy] = lc::linear_taps(X, Y);
                     int s00[C], s01[C], s10[C], s11[C];
                     tap(sx, sy, s00);
                     tap(sx + 1, sy, s01);
@@ -182,7 +147,7 @@ __global__ __launch_bounds__(kThreads) void lc_crop_warp_kernel(const Params p) 
 #pragma unroll
                     for (int c = 0; c < C; ++c) v[c] = (w00 * s00[c] + w01 * s01[c] + w10 * s10[c] + w11 * s11[c] + 512) >> 10;
                 } else {
-                    tap((int)(X >> 10), (int)(Y >> 10), v);
+                    tap(lc::nearest_tap(X), lc::nearest_tap(Y), v);
                 }
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
@@ -247,16 +212,12 @@ int lc_crop_warp_u8(const unsigned char* frames, int F, int H, int W, int C, con
     p.out = out;
     p.info = info;
     p.F = F, p.H = H, p.W = W, p.B = B, p.h = h, p.w = w;
-    const int quads = (w + 3) / 4;
-    while ((1 << p.lg_tx) < quads && (1 << p.lg_tx) < kThreads) ++p.lg_tx;
-    const int rows_per_pass = kThreads >> p.lg_tx;
-    p.band = rows_per_pass > kMinBand ? rows_per_pass : kMinBand;
-    p.nbands = (h + p.band - 1) / p.band;
+    p.grid = lc::warp_grid(h, w, kThreads, kMinBand);
     const size_t elem = out_dtype == LC_CROP_U8 ? 1 : out_dtype == LC_CROP_F32 ? 4 : 2;
     p.vec = (w % 4 == 0) && (reinterpret_cast<uintptr_t>(out) % (4 * elem) == 0);
     p.normalize = mean != nullptr;
     for (int c = 0; c < C && mean; ++c) p.mean[c] = mean[c], p.std[c] = std[c];
-    const long long blocks = (long long)B * p.nbands;
+    const long long blocks = (long long)B * p.grid.nbands;
     if (blocks > 0x7fffffffLL) return fail(9, "lc_crop_warp_u8: too many rows and bands for one launch");
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (out_dtype) {

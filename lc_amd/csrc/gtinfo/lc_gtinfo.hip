@@ -2,8 +2,7 @@
 // annotation record and the visible mask per instance out (lc_gtinfo_f32); and, for scenes without a measured depth, the scene's depth
 // as the per-pixel minimum over its instances' renders (lc_scene_compose_f32).  The exact definition of every output is
 // include/lc_amd_gtinfo.h; tests/gtinfo_oracle.py is its numpy restatement.  The renders come from lc_amd.render.render_depth
-// (lc_amd/gtinfo.py chains them) or from any other renderer.  The ray-length arithmetic is that of the VSD score, restated: this library
-// includes nothing but its own header.
+// (lc_amd/gtinfo.py chains them) or from any other renderer.  Ray length and group loads: shared/lc_ray_length.h, with the VSD score.
 //
 // Launch shape.  An instance's (h,w) window is cut into tiles of kTileH rows by kGroups groups of four pixels, one workgroup of four
 // wavefronts per (instance, tile); inside a tile the items are (row, group), flattened, so a 192-pixel window row leaves no lane idle.
@@ -28,6 +27,8 @@
 #include <string>
 
 #include "../../../include/lc_amd_gtinfo.h"
+#include "../shared/lc_ray_length.h"
+#include "../shared/lc_wave_int.h"
 
 #ifndef LC_AMD_GTINFO_SRC_HASH
 #define LC_AMD_GTINFO_SRC_HASH "unrecorded"
@@ -106,19 +107,6 @@ __device__ __forceinline__ Tile tile_of(const Window& p, int tiles_x, int tiles_
     return t;
 }
 
-__device__ __forceinline__ int lead_of(const float* row) { return (int)((reinterpret_cast<uintptr_t>(row) >> 2) & 3); }  // elements behind the 16-byte boundary
-
-// the four elements of a row of width w from x on, 0 outside the row; a whole group starts on a 16-byte boundary by construction
-__device__ __forceinline__ void load_group(const float* row, int x, int w, float (&f)[4]) {
-    if (x >= 0 && x + 4 <= w) {
-        const float4 v = *reinterpret_cast<const float4*>(row + x);
-        f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) f[j] = (x + j >= 0 && x + j < w) ? row[x + j] : 0.0f;
-    }
-}
-
 __device__ __forceinline__ void store_mask(unsigned char* row, int x, int w, unsigned bits) {
     if (x >= 0 && x + 4 <= w && (reinterpret_cast<uintptr_t>(row + x) & 3) == 0) {
         *reinterpret_cast<unsigned*>(row + x) = bits;
@@ -134,22 +122,6 @@ struct Record {
     int ox0, oy0, ox1, oy1;  // obj: minima, maxima
     int vx0, vy0, vx1, vy1;  // visib
 };
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int m = kWave / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
-    return v;
-}
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-    for (int m = kWave / 2; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m, kWave));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int m = kWave / 2; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m, kWave));
-    return v;
-}
 
 // column j of the record: 0 a sum, 1 a minimum, 2 a maximum
 __device__ __host__ __forceinline__ int kind_of(int j) { return j < kSums ? 0 : (((j - kSums) & 3) < 2 ? 1 : 2); }
@@ -212,12 +184,8 @@ __global__ __launch_bounds__(kThreads) void lc_gtinfo_reduce_kernel(const InfoPa
                     for (int j = 0; j < 4; ++j)
                         if (x + j >= 0 && x + j < w && X + j >= 0 && X + j < W) ft[j] = test[off + j];
                 }
-                double py = (double)Y;
-                py = py + pcy;
-                py = py - k12;
-                const double Yk = py / k11;
-                yy = Yk * Yk;
-                kY = k01 * Yk;
+                const RayRow r = ray_row(Y, pcy, k12, k11, k01);
+                yy = r.yy, kY = r.kY;
             }
             const bool row_edge = y == 0 || y == h - 1;
 #pragma unroll
@@ -233,15 +201,7 @@ __global__ __launch_bounds__(kThreads) void lc_gtinfo_reduce_kernel(const InfoPa
                 bool vis = missing;
                 if (!missing) {
                     a.n_valid += 1;
-                    double px = (double)Xj;
-                    px = px + pcx;
-                    px = px - k02;
-                    const double num = px - kY;
-                    const double Xk = num / k00;
-                    const double xx = Xk * Xk;
-                    double s = xx + yy;
-                    s = s + 1.0;
-                    const double n = sqrt(s);
+                    const double n = ray_length(Xj, pcx, k02, k00, kY, yy);
                     const double dist_g = (double)fg[j] * n;
                     const double dist_t = (double)ft[j] * n;
                     const double over = dist_g - dist_t;

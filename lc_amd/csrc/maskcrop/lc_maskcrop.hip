@@ -3,11 +3,7 @@
 // exact definition of every output in include/lc_amd_maskcrop.h; tests/maskcrop_oracle.py is its numpy restatement).  What the
 // reference's loader does per instance on a host core (dataset.py:414,425-442).
 //
-// The coordinate arithmetic is that of the zoom-in crops (include/lc_amd_crop.h), RESTATED here, not shared: this library includes
-// nothing but its own header, and both are held to tests/crops_oracle.coordinates.  It is written with __dmul_rn / __dadd_rn: the
-// library is built with -ffp-contract=on, and m01 * y + b1 in one expression would be fused and can move X by one.
-//
-// Warp launch: one workgroup of four waves per (row, band of crop rows), as in lc_crop.hip.  Thread 0 forms the row's inverse in fp64
+// Warp launch, as in lc_crop.hip (shared/lc_warp_grid.h): four waves per (row, band of crop rows).  Thread 0 forms the row's inverse in fp64
 // and judges the row; a thread owns four consecutive x (its two x terms are formed once) and walks the band's rows.  Per pixel the ONE
 // pair of 64-bit sums gives both coordinate sets (+ 512 for the nearest tap, + 16 for the four linear ones); the taps are bytes of the
 // window, each judged on its own against the window; the linear value is an integer k <= 1024 times 2^-10.  A thread stores four
@@ -30,6 +26,8 @@
 #include <string>
 
 #include "../../../include/lc_amd_maskcrop.h"
+#include "../shared/lc_warp_grid.h"
+#include "../shared/lc_wave_int.h"
 
 #ifndef LC_AMD_MASKCROP_SRC_HASH
 #define LC_AMD_MASKCROP_SRC_HASH "unrecorded"
@@ -51,9 +49,7 @@ constexpr int kWave = 64;
 constexpr int kWaves = kThreads / kWave;
 constexpr int kCkThreads = 1024;
 constexpr int kMaxCheck = LC_MASKCROP_MAX_CHECK;
-constexpr int kMinBand = 16;                // crop rows per workgroup (more where a pass of the workgroup covers more)
-constexpr double kAbScale = 1024.0;         // 1 << AB_BITS
-constexpr double kFixLimit = 1073741824.0;  // 2^30
+constexpr int kMinBand = 16;  // crop rows per workgroup (more where a pass of the workgroup covers more)
 
 struct Params {
     const unsigned char* masks;  // (F,Hm,Wm)
@@ -67,21 +63,11 @@ struct Params {
     void* ck;                    // (B,n_check,2) int32 / int64
     int* info;                   // (B) or null
     int F, Hm, Wm, B, h, w;
-    int band, nbands;            // crop rows per workgroup, workgroups per row of the batch
-    int lg_tx;                   // log2 of the threads along x
+    WarpGrid grid;
     int vec_vis, vec_noc;        // four-pixel stores are possible
     int valid_th, n_check, ck64;
     unsigned seed_lo, seed_hi;
 };
-
-// rint (half to even), clamped to +-2^30, as an integer.  fmax / fmin also turn a NaN into a bound.
-__device__ inline int fix(double v) { return (int)fmin(fmax(rint(v), -kFixLimit), kFixLimit); }
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int m = kWave / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
-    return v;
-}
 
 __global__ __launch_bounds__(kThreads) void lc_mask_zero_kernel(int* cnt, int B) {
     const int b = blockIdx.x * kThreads + threadIdx.x;
@@ -95,28 +81,13 @@ __global__ __launch_bounds__(kThreads) void lc_mask_warp_kernel(const Params p) 
     __shared__ int s_cnt[kWaves];
 
     const int tid = threadIdx.x;
-    const int b = blockIdx.x / p.nbands, band = blockIdx.x - b * p.nbands;
+    const int b = blockIdx.x / p.grid.nbands, band = blockIdx.x - b * p.grid.nbands;
     if (tid == 0) {
         const int f = p.mask_index ? p.mask_index[b] : b;
         const int ox = p.origin ? p.origin[2 * (size_t)b] : 0, oy = p.origin ? p.origin[2 * (size_t)b + 1] : 0;
         bool ok = f >= 0 && f < p.F;
         ok = ok && ox >= -LC_MASKCROP_MAX_ORIGIN && ox <= LC_MASKCROP_MAX_ORIGIN && oy >= -LC_MASKCROP_MAX_ORIGIN && oy <= LC_MASKCROP_MAX_ORIGIN;
-        double M[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            const float m = p.M[6 * (size_t)b + k];
-            ok = ok && (__float_as_uint(m) & 0x7f800000u) != 0x7f800000u;
-            M[k] = (double)m;
-        }
-        double D = __dadd_rn(__dmul_rn(M[0], M[4]), -__dmul_rn(M[1], M[3]));
-        D = D != 0.0 ? 1.0 / D : 0.0;
-        const double m00 = __dmul_rn(M[4], D), m01 = __dmul_rn(-M[1], D), m10 = __dmul_rn(-M[3], D), m11 = __dmul_rn(M[0], D);
-        s_inv[0] = m00;
-        s_inv[1] = m01;
-        s_inv[2] = __dadd_rn(__dmul_rn(-m00, M[2]), -__dmul_rn(m01, M[5]));
-        s_inv[3] = m10;
-        s_inv[4] = m11;
-        s_inv[5] = __dadd_rn(__dmul_rn(-m10, M[2]), -__dmul_rn(m11, M[5]));
+        ok = inverse_of(p.M + 6 * (size_t)b, ok, s_inv);
         s_src[0] = ok ? f : -1;
         s_src[1] = ok ? ox : 0;
         s_src[2] = ok ? oy : 0;
@@ -132,10 +103,10 @@ __global__ __launch_bounds__(kThreads) void lc_mask_warp_kernel(const Params p) 
     float* vis = p.vis ? p.vis + row0 : nullptr;
     unsigned char* noc = p.noc ? p.noc + row0 : nullptr;
 
-    const int TX = 1 << p.lg_tx, TY = kThreads >> p.lg_tx;
-    const int tx = tid & (TX - 1), ty = tid >> p.lg_tx;
+    const int TX = 1 << p.grid.lg_tx, TY = kThreads >> p.grid.lg_tx;
+    const int tx = tid & (TX - 1), ty = tid >> p.grid.lg_tx;
     const int quads = (p.w + 3) >> 2;
-    const int y_end = min(p.h, (band + 1) * p.band);
+    const int y_end = min(p.h, (band + 1) * p.grid.band);
 
     // frame pixel (xx, yy) as 0 / 1: the window's byte, 0 outside the window
     auto tap = [&](int xx, int yy) -> int {
@@ -149,27 +120,19 @@ __global__ __launch_bounds__(kThreads) void lc_mask_warp_kernel(const Params p) 
     for (int xq = tx; xq < quads; xq += TX) {
         const int x0 = xq << 2;
         int ax[4], ay[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const double x = (double)(x0 + j);
-            ax[j] = fix(__dmul_rn(__dmul_rn(m00, x), kAbScale));
-            ay[j] = fix(__dmul_rn(__dmul_rn(m10, x), kAbScale));
-        }
-        for (int y = band * p.band + ty; y < y_end; y += TY) {
-            const double yd = (double)y;
-            const long long X0 = (long long)fix(__dmul_rn(__dadd_rn(__dmul_rn(m01, yd), b1), kAbScale));
-            const long long Y0 = (long long)fix(__dmul_rn(__dadd_rn(__dmul_rn(m11, yd), b2), kAbScale));
+        quad_terms(m00, m10, x0, ax, ay);
+        for (int y = band * p.grid.band + ty; y < y_end; y += TY) {
+            const long long X0 = row_term(m01, b1, y), Y0 = row_term(m11, b2, y);
             float rv[4];
             unsigned bits = 0;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const long long X = X0 + ax[j], Y = Y0 + ay[j];
-                const int n = tap((int)((X + 512) >> 10), (int)((Y + 512) >> 10));
+                const int n = tap(nearest_tap(X + kNearestDelta), nearest_tap(Y + kNearestDelta));
                 if (x0 + j < p.w) count += n;
                 bits |= (unsigned)n << (8 * j);
                 if constexpr (LINEAR) {
-                    const int Xs = (int)((X + 16) >> 5), Ys = (int)((Y + 16) >> 5);
-                    const int sx = Xs >> 5, sy = Ys >> 5, fx = Xs & 31, fy = Ys & 31;
+                    const auto [sx, sy, fx, fy] = linear_taps(X + kLinearDelta, Y + kLinearDelta);
                     const int k = (32 - fx) * (32 - fy) * tap(sx, sy) + fx * (32 - fy) * tap(sx + 1, sy) + (32 - fx) * fy * tap(sx, sy + 1) +
                                   fx * fy * tap(sx + 1, sy + 1);
                     rv[j] = (float)k * 0.0009765625f;  // k 2^-10: exact
@@ -416,14 +379,10 @@ int lc_mask_crops_u8(const unsigned char* masks, int F, int Hm, int Wm, const in
         }
         if (!p.noc) p.noc = ws;
     }
-    const int quads = (w + 3) / 4;
-    while ((1 << p.lg_tx) < quads && (1 << p.lg_tx) < lc::kThreads) ++p.lg_tx;
-    const int rows_per_pass = lc::kThreads >> p.lg_tx;
-    p.band = rows_per_pass > lc::kMinBand ? rows_per_pass : lc::kMinBand;
-    p.nbands = (h + p.band - 1) / p.band;
+    p.grid = lc::warp_grid(h, w, lc::kThreads, lc::kMinBand);
     p.vec_vis = (w % 4 == 0) && !lc::misaligned(p.vis, 16);
     p.vec_noc = (w % 4 == 0) && !lc::misaligned(p.noc, 4);
-    const long long blocks = (long long)B * p.nbands;
+    const long long blocks = (long long)B * p.grid.nbands;
     if (blocks > 0x7fffffffLL) return fail(11, me + "too many rows and bands for one launch");
 
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -10,8 +10,8 @@
 // groups at both ends of a row -- four guarded 4-byte loads each.  The choice is uniform over a row.
 //
 // Arithmetic.  Most pixels of a frame see neither rendering and are done after three loads and two compares.  The others take one fp64
-// division and one square root for the ray length (Y's division is shared by a group), three products, and the comparisons of steps 2 to 4.
-// -ffp-contract=on fuses only inside one expression, so every product and sum below is a statement of its own.
+// division and one square root for the ray length (shared/lc_ray_length.h; Y's division is shared by a group), three products, and the
+// comparisons of steps 2 to 4.  -ffp-contract=on fuses only inside one expression, so every product and sum below is a statement of its own.
 //
 // Counting.  Each lane keeps 3 + T integer counters in registers; a wavefront that counted anything sums them with a butterfly, the four
 // wavefronts meet in LDS, and a workgroup adds its non-zero sums to counts[b] with integer atomics.  Integer addition is associative: the counts are the same
@@ -23,6 +23,8 @@
 #include <string>
 
 #include "../../../include/lc_amd_vsd.h"
+#include "../shared/lc_ray_length.h"
+#include "../shared/lc_wave_int.h"
 
 #ifndef LC_AMD_VSD_SRC_HASH
 #define LC_AMD_VSD_SRC_HASH "unrecorded"
@@ -87,15 +89,7 @@ __device__ __forceinline__ void pixel(float fe, float fg, float ft, int xf, doub
     const bool he = fe > 0.0f, hg = fg > 0.0f;
     if (!(he || hg)) return;
     a.n_edge += border ? 1 : 0;
-    double px = (double)xf;
-    px = px + c.pcx;
-    px = px - c.k02;
-    const double num = px - kY;
-    const double X = num / c.k00;
-    const double xx = X * X;
-    double s = xx + yy;
-    s = s + 1.0;
-    const double n = sqrt(s);
+    const double n = ray_length(xf, c.pcx, c.k02, c.k00, kY, yy);
     const bool missing = !(ft > 0.0f);
     const double dist_e = (double)fe * n;
     const double dist_g = (double)fg * n;
@@ -112,12 +106,6 @@ __device__ __forceinline__ void pixel(float fe, float fg, float ft, int xf, doub
         for (int k = 0; k < kMaxT; ++k)
             if (k < T) a.cost[k] += diff >= thr[k] ? 1 : 0;
     }
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int m = kWave / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
-    return v;
 }
 
 __device__ __forceinline__ bool aligned16(const float* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
@@ -163,7 +151,7 @@ __global__ __launch_bounds__(kThreads) void lc_vsd_count_kernel(const VsdParams 
         const float* e_row = est + (size_t)y * w;
         const float* g_row = gt + (size_t)y * w;
         const float* t_row = test + (size_t)y * p.W;
-        const int lead = (int)((reinterpret_cast<uintptr_t>(e_row) >> 2) & 3);  // elements behind the 16-byte boundary
+        const int lead = lead_of(e_row);
         const int x = 4 * g - lead;
         if (x >= w) continue;
         float fe[4], fg[4], ft[4];
@@ -187,18 +175,13 @@ __global__ __launch_bounds__(kThreads) void lc_vsd_count_kernel(const VsdParams 
 #pragma unroll
         for (int j = 0; j < 4; ++j) any = any || fe[j] > 0.0f || fg[j] > 0.0f;
         if (!any) continue;
-        double py = (double)(y + row.y0);
-        py = py + c.pcy;
-        py = py - c.k12;
-        const double Y = py / c.k11;
-        const double yy = Y * Y;
-        const double kY = c.k01 * Y;
+        const RayRow r = ray_row(y + row.y0, c.pcy, c.k12, c.k11, c.k01);
         const bool row_cut = (y == 0 && cut_t) || (y == h - 1 && cut_b);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int xj = x + j;  // a pixel outside the row holds zeros and counts nothing
             const bool border = row_cut || (xj == 0 && cut_l) || (xj == w - 1 && cut_r);
-            pixel(fe[j], fg[j], ft[j], xj + row.x0, yy, kY, border, c, thr, T, a);
+            pixel(fe[j], fg[j], ft[j], xj + row.x0, r.yy, r.kY, border, c, thr, T, a);
         }
     }
 

@@ -3,11 +3,14 @@ small windows of 5 x 7 up to 48 x 40, matrices from the identity to the stretche
 on both sides of zero, crops that straddle each window edge or miss the window.  The crop sizes follow the warp launch's shape: a
 workgroup covers a band of 16 crop rows (more where the crop is narrower than 64), its 256 threads laid out as 16 x 16 quads of four
 pixels at w = 64, so 16 x 64 is one pass of one workgroup exactly; a row more starts a second band, a column more a second quad layout
-(32 x 8) with a partial quad."""
+(32 x 8) with a partial quad.  Two 16 x 16 rows hold the device to the coordinate traps of tests/crops_cases.py: its "ties" matrix, and a
+matrix on which contracting m01 * y + b1 into one fma changes the mask crop."""
 import math
 from typing import NamedTuple
 
 import numpy as np
+
+from tests import crops_oracle, maskcrop_oracle
 
 TILE_H, TILE_W = 16, 64
 EYE = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0))
@@ -56,6 +59,42 @@ def affine(center, zoom, out_hw, rot=0.0, stretch=1.0, skew=0.0, shift=(0.0, 0.0
     return tuple(map(tuple, np.concatenate((A, t[:, None]), 1).astype(np.float32).tolist()))
 
 
+def planted(window, origin, M, out_hw, vis_interp, mistake):
+    """maskcrop_oracle.warp_row with its coordinates taken from crops_oracle.coordinates(..., mistake=mistake)."""
+    real = crops_oracle.coordinates
+    crops_oracle.coordinates = lambda M_, out_hw_, interp, mistake_=None: real(M_, out_hw_, interp, mistake)
+    try:
+        return maskcrop_oracle.warp_row(window, origin, M, out_hw, vis_interp)
+    finally:
+        crops_oracle.coordinates = real
+
+
+def moved_by(window, origin, M, out_hw, mistake):
+    """The number of pixels of (msk_vis linear, msk_noc) that the planted mistake changes."""
+    good, bad = maskcrop_oracle.warp_row(window, origin, M, out_hw), planted(window, origin, M, out_hw, maskcrop_oracle.LINEAR, mistake)
+    return int((good[0] != bad[0]).sum()), int((good[1] != bad[1]).sum())
+
+
+def find_fma_row(window, origin, out_hw=(16, 16), tries=4000):
+    """A matrix on which contracting m01 * y + b1 into one fma changes the mask crop of this window: the one tests/crops_cases.py finds
+    for its frame if it qualifies here too, else the same seeded search judged on the window; None when no candidate qualifies."""
+    from tests import crops_cases
+
+    M = dict(crops_cases.CASES)["fma-row"]
+    if any(moved_by(window, origin, M, out_hw, "fma")):
+        return M
+    rng = np.random.default_rng(crops_cases.SEED)
+    for _ in range(tries):
+        a, c = float(rng.choice([3, 5, 6, 7])), float(rng.choice([-2, -1, 1, 2]))
+        y0, j = int(rng.integers(1, 16)), int(rng.integers(64, 900))
+        m01 = crops_oracle.inverse(crops_cases._m(a, c, 0, 0, 1, 0))[1]
+        b1 = (32 * j + 15 + 0.5) / 1024.0 - m01 * y0
+        M = crops_cases._m(a, c, -a * b1, 0, 1, 0)
+        if any(moved_by(window, origin, M, out_hw, "fma")):
+            return M
+    return None
+
+
 def _centre(mask_hw, origin):
     return (origin[0] + mask_hw[1] * 0.5, origin[1] + mask_hw[0] * 0.5)
 
@@ -83,6 +122,15 @@ def _warps():
     add("edge-top", (12, 14), -1, (-30, -40), (18, 19), zoom=1.3, shift=(0.0, 5.9), rot=0.1)
     add("edge-bottom", (12, 14), -1, (-30, -40), (18, 19), zoom=1.3, shift=(0.0, -6.1), rot=-0.1)
     add("window-outside", (12, 14), -1, (200, 300), (18, 19), M=EYE)
+    # the coordinate traps of the zoom-in crops, on a mask window
+    from tests import crops_cases
+
+    as_rows = lambda M: tuple(map(tuple, np.asarray(M, dtype=np.float32).tolist()))
+    add("ties", (48, 40), 12, (0, 0), (16, 16), M=as_rows(dict(crops_cases.CASES)["ties"]))
+    fma = find_fma_row(mask((48, 40), 13), (0, 0))
+    if fma is None:  # the row that pins the contraction trap must not go missing without a word
+        raise RuntimeError("tests/maskcrop_cases.py: the seeded search found no matrix on which fma contraction changes the mask crop")
+    add("fma-row", (48, 40), 13, (0, 0), (16, 16), M=as_rows(fma))
     return tuple(out)
 
 

@@ -118,7 +118,8 @@ def test_embedded_source_hash_and_separate_sources():
         assert not any("crop" in os.path.basename(s) or os.sep + "crop" + os.sep in s for s in build._deps(t))
     assert len({build.source_hash(t) for t in build.all_targets()}) == 5
     src = open(build.sources(build.CROP)[0]).read()
-    assert re.findall(r'#include "([^"]+)"', src) == ["../../../include/lc_amd_crop.h"]
+    assert re.findall(r'#include "([^"]+)"', src) == ["../../../include/lc_amd_crop.h", "../shared/lc_warp_grid.h"]
+    assert build.CROP.shared == (build.WARP_GRID_H,)
 
 
 def _call(lib, **over):

@@ -21,7 +21,7 @@ def test_build_group_and_order(monkeypatch):
     assert build.annot_targets() == (build.GTINFO,)
     earlier = build.all_targets() + build.tool_targets() + build.eval_targets() + build.scene_targets()
     assert len(earlier) == 8 and build.GTINFO not in earlier
-    assert build.GTINFO.so_path.endswith(os.path.join("_C", "liblc_amd_gtinfo.so")) and build.GTINFO.header == "lc_amd_gtinfo.h" and build.GTINFO.shared == ()
+    assert build.GTINFO.so_path.endswith(os.path.join("_C", "liblc_amd_gtinfo.so")) and build.GTINFO.header == "lc_amd_gtinfo.h" and build.GTINFO.shared == (build.RAY_LENGTH_H, build.WAVE_INT_H)
     asked, real = [], build.build
     monkeypatch.setattr(build, "build", lambda force=False, verbose=False, target=build.MAIN: (asked.append(target), real(force, verbose, target))[1])
     entry.build()
@@ -73,9 +73,9 @@ def test_source_hash_is_its_own():
     for t in others:  # no other library sees this directory or header, and this one adds no file to theirs
         assert not any(mine(d) for d in build._deps(t)), t.name
         assert build.embedded_hash(t.so_path, T.hash_marker) is None, t.name
-    assert all(mine(d) for d in build._deps(T))
+    assert all(mine(d) or d in (build.RAY_LENGTH_H, build.WAVE_INT_H) for d in build._deps(T))  # its own, or exactly the shared headers it declares
     src = open(build.sources(T)[0]).read()
-    assert set(re.findall(r'#include "([^"]+)"', src)) == {"../../../include/lc_amd_gtinfo.h"}
+    assert set(re.findall(r'#include "([^"]+)"', src)) == {"../../../include/lc_amd_gtinfo.h", "../shared/lc_ray_length.h", "../shared/lc_wave_int.h"}
 
 
 def _good(B=3, h=4, w=5):

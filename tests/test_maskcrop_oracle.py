@@ -60,6 +60,22 @@ def test_msk_noc_is_the_8_bit_oracles_nearest_warp(case):
     assert np.array_equal(noc.astype(bool), ref)
 
 
+def test_the_case_list_notices_a_contracted_row_term():
+    """The fma row: forming m01 * y + b1 with one rounding (crops_oracle's planted mistake "fma") moves at least one pixel of msk_noc or
+    msk_vis there, so a device copy of the coordinates that lets the compiler contract that expression cannot pass test_gpu_maskcrop."""
+    by_name = {c.name: c for c in cases.WARPS}
+    case = by_name["fma-row"]
+    assert case.out_hw == (16, 16) and case.mask_hw[0] <= 48 and case.mask_hw[1] <= 40 and by_name["ties"].out_hw == (16, 16)
+    window = cases.mask(case.mask_hw, case.seed)
+    vis, noc = cases.moved_by(window, case.origin, case.M, case.out_hw, "fma")
+    print("pixels moved by the contraction: msk_vis", vis, "msk_noc", noc)
+    assert vis + noc >= 1
+    assert crops_oracle.coordinates is cases.crops_oracle.coordinates and cases.moved_by(window, case.origin, case.M, case.out_hw, None) == (0, 0)
+    from tests import crops_cases
+
+    assert np.array_equal(np.asarray(by_name["ties"].M, dtype=np.float32), dict(crops_cases.CASES)["ties"])
+
+
 @pytest.mark.parametrize("valid,n_check", [(1, 256), (2, 255), (100, 256), (255, 256), (256, 256), (257, 256), (300, 1), (4096, 256), (7, 20)])
 def test_every_round_is_a_permutation(valid, n_check):
     noc = cases.noc_with(valid, (64, 64), seed=valid)
@@ -138,7 +154,7 @@ def test_build_group_header_exports_and_source_hash():
     assert build.loader_targets() == (T,)
     others = build.all_targets() + build.tool_targets() + build.eval_targets() + build.scene_targets() + build.annot_targets()
     assert len(others) == 9 and T not in others
-    assert T.so_path.endswith(os.path.join("_C", "liblc_amd_maskcrop.so")) and T.header == "lc_amd_maskcrop.h" and T.shared == ()
+    assert T.so_path.endswith(os.path.join("_C", "liblc_amd_maskcrop.so")) and T.header == "lc_amd_maskcrop.h" and T.shared == (build.WARP_GRID_H, build.WAVE_INT_H)
     lib = maskcrop.load()
     assert not build.is_stale(T)
     assert lib.lc_amd_maskcrop_source_hash().decode() == build.source_hash(T) == build.embedded_hash(T.so_path, T.hash_marker)
@@ -149,9 +165,9 @@ def test_build_group_header_exports_and_source_hash():
 
     for t in others:  # no other library sees this directory or header
         assert not any(mine(d) for d in build._deps(t)), t.name
-    assert all(mine(d) for d in build._deps(T))
+    assert all(mine(d) or d in (build.WARP_GRID_H, build.WAVE_INT_H) for d in build._deps(T))  # its own, or exactly the shared headers it declares
     src = open(build.sources(T)[0]).read()
-    assert set(re.findall(r'#include "([^"]+)"', src)) == {"../../../include/lc_amd_maskcrop.h"}
+    assert set(re.findall(r'#include "([^"]+)"', src)) == {"../../../include/lc_amd_maskcrop.h", "../shared/lc_warp_grid.h", "../shared/lc_wave_int.h"}
     doc = build.__doc__
     assert "liblc_amd_maskcrop.so" in doc and "lc_amd/csrc/maskcrop/" in doc and "include/lc_amd_maskcrop.h" in doc
 

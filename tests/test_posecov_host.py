@@ -49,12 +49,16 @@ def _quoted_includes(path):
 
 def test_every_library_hashes_every_file_it_includes(tmp_path, monkeypatch):
     """A library's hash sees every edit that can change it: whatever its .hip and .h files include with quotes, followed through the
-    included files, is one of the files the hash is taken over; the shared header belongs to the two libraries that include it."""
+    included files, is one of the files the hash is taken over, for EVERY library; a shared header belongs to exactly the libraries that
+    include it."""
     import shutil
 
     from lc_amd import build
 
-    for t in build.all_targets():
+    every = build.every_target()
+    assert every == (build.all_targets() + build.tool_targets() + build.eval_targets() + build.scene_targets() + build.annot_targets() +
+                     build.loader_targets()) and len(every) == 10
+    for t in every:
         deps = {os.path.normpath(d) for d in build._deps(t)}
         assert all(os.path.exists(d) for d in deps), t.name
         seen, todo = set(), sorted(deps)
@@ -85,6 +89,16 @@ def test_every_library_hashes_every_file_it_includes(tmp_path, monkeypatch):
         f.write(b"\n")
     after = [build.source_hash(t) for t in copies]
     assert [t.name for t, x, y in zip(copies, before, after) if x != y] == ["main", "posecov"]
+
+    # the same for the headers of the image libraries, over every library: one more byte changes exactly the hashes of those that include it
+    copies = [t._replace(src_dir=moved(t.src_dir), shared=tuple(moved(s) for s in t.shared)) for t in every]
+    for header, users in ((build.WARP_GRID_H, ["crop", "maskcrop"]), (build.RAY_LENGTH_H, ["vsd", "gtinfo"]), (build.WAVE_INT_H, ["vsd", "gtinfo", "maskcrop"])):
+        assert [t.name for t in every if header in _quoted_includes(build.sources(t)[0])] == users == [t.name for t in every if header in t.shared]
+        before = [build.source_hash(t) for t in copies]
+        with open(moved(header), "ab") as f:
+            f.write(b"\n")
+        after = [build.source_hash(t) for t in copies]
+        assert [t.name for t, x, y in zip(copies, before, after) if x != y] == users, header
 
 
 def test_entry_point_checks_its_arguments():

@@ -26,7 +26,7 @@ def test_build_groups(monkeypatch):
     assert build.scene_targets() == (build.VSD,)
     assert build.all_targets() == (build.MAIN, build.OPTIM, build.POSECOV, build.RENDER, build.CROP)
     assert build.tool_targets() == (build.MODELS,) and build.eval_targets() == (build.SYMERR,)
-    assert build.VSD.so_path.endswith(os.path.join("_C", "liblc_amd_vsd.so")) and build.VSD.header == "lc_amd_vsd.h" and build.VSD.shared == ()
+    assert build.VSD.so_path.endswith(os.path.join("_C", "liblc_amd_vsd.so")) and build.VSD.header == "lc_amd_vsd.h" and build.VSD.shared == (build.RAY_LENGTH_H, build.WAVE_INT_H)
     # the entry point's build() hands every group to the builder, the new one included, and leaves the library in place and current
     asked, real = [], build.build
     monkeypatch.setattr(build, "build", lambda force=False, verbose=False, target=build.MAIN: (asked.append(target), real(force, verbose, target))[1])
@@ -68,9 +68,10 @@ def test_source_hash_is_its_own():
     for t in others:  # no other library sees this directory or header, and this one adds no file to theirs
         assert not any(os.sep + "vsd" + os.sep in d or d.endswith("lc_amd_vsd.h") for d in build._deps(t)), t.name
         assert build.embedded_hash(t.so_path, build.VSD.hash_marker) is None, t.name
-    assert all(os.sep + "vsd" + os.sep in d or d.endswith("lc_amd_vsd.h") for d in build._deps(build.VSD))
+    # every dependency is the library's own, or one of exactly the shared headers it declares
+    assert all(os.sep + "vsd" + os.sep in d or d.endswith("lc_amd_vsd.h") or d in (build.RAY_LENGTH_H, build.WAVE_INT_H) for d in build._deps(build.VSD))
     src = open(build.sources(build.VSD)[0]).read()
-    assert set(re.findall(r'#include "([^"]+)"', src)) == {"../../../include/lc_amd_vsd.h"}
+    assert set(re.findall(r'#include "([^"]+)"', src)) == {"../../../include/lc_amd_vsd.h", "../shared/lc_ray_length.h", "../shared/lc_wave_int.h"}
     assert not os.path.exists(os.path.join(build.CSRC, "render", "lc_vsd.hip"))
 
 
