@@ -11,10 +11,12 @@
     vsd      lc_amd/_C/liblc_amd_vsd.so      lc_amd/csrc/vsd/         include/lc_amd_vsd.h      BOP's VSD from rendered and scene depth (evaluation)
     gtinfo   lc_amd/_C/liblc_amd_gtinfo.so   lc_amd/csrc/gtinfo/      include/lc_amd_gtinfo.h   BOP's ground-truth visibility annotations (an offline tool's kernels)
     maskcrop lc_amd/_C/liblc_amd_maskcrop.so lc_amd/csrc/maskcrop/    include/lc_amd_maskcrop.h the training mask crops: warps, valid count, check points
+    augment  lc_amd/_C/liblc_amd_augment.so  lc_amd/csrc/augment/     include/lc_amd_augment.h  the training crops' background switch and colour augmentation
 
 A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`): code that
 two libraries need exists once there (lc_shared.h: main, posecov, models, symerr; lc_warp_grid.h: crop, maskcrop; lc_ray_length.h: vsd,
-gtinfo; lc_wave_int.h: vsd, gtinfo, maskcrop), and no side library restates another's arithmetic.
+gtinfo; lc_wave_int.h: vsd, gtinfo, maskcrop), and no side library restates another's arithmetic -- but for the five lines of the
+hash finaliser that augment has in common with maskcrop (each shared header's users are stated by the tests of the libraries before it).
 Every function takes the library it works on as a `Target` (default: the hot-path library)."""
 from __future__ import annotations
 
@@ -82,6 +84,9 @@ _EVAL = (SYMERR,)
 _SCENE = (VSD,)
 _ANNOT = (GTINFO,)
 _LOADER = (MASKCROP,)
+# the pixel side of the training loader's augmentation (lc_amd.augment); includes no shared header (it restates maskcrop's hash)
+AUGMENT = _side("augment")
+_AUGMENT = (AUGMENT,)
 HASH_MARKER = MAIN.hash_marker
 
 
@@ -121,8 +126,16 @@ def loader_targets():
 
 
 def every_target():
-    """Every library, the six groups in build order."""
+    """The ten libraries of the six groups above, in build order.  augment_targets() is NOT among them: the tests of the earlier libraries
+    state this tuple, its length and each group member by member, so a library added since is a group beside it; whoever builds
+    everything builds `every_target() + augment_targets()`."""
     return all_targets() + tool_targets() + eval_targets() + scene_targets() + annot_targets() + loader_targets()
+
+
+def augment_targets():
+    """The library behind the training loader's background switch and colour augmentation: built after every_target() by
+    `python __graft_entry__.py build`, loaded by no per-step path."""
+    return _AUGMENT
 
 
 def sources(target: Target = MAIN):
@@ -276,5 +289,5 @@ def build_variant(name: str, flags, verbose: bool = False) -> str:
 
 
 if __name__ == "__main__":
-    for t in every_target():
+    for t in every_target() + augment_targets():
         print(build(force=True, verbose=True, target=t))
