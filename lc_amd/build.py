@@ -12,11 +12,13 @@
     gtinfo   lc_amd/_C/liblc_amd_gtinfo.so   lc_amd/csrc/gtinfo/      include/lc_amd_gtinfo.h   BOP's ground-truth visibility annotations (an offline tool's kernels)
     maskcrop lc_amd/_C/liblc_amd_maskcrop.so lc_amd/csrc/maskcrop/    include/lc_amd_maskcrop.h the training mask crops: warps, valid count, check points
     augment  lc_amd/_C/liblc_amd_augment.so  lc_amd/csrc/augment/     include/lc_amd_augment.h  the training crops' background switch and colour augmentation
+    rle      lc_amd/_C/liblc_amd_rle.so      lc_amd/csrc/rle/         include/lc_amd_rle.h      the store of COCO run-length masks: index, decode, encode
 
 A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`): code that
 two libraries need exists once there (lc_shared.h: main, posecov, models, symerr; lc_warp_grid.h: crop, maskcrop; lc_ray_length.h: vsd,
 gtinfo; lc_wave_int.h: vsd, gtinfo, maskcrop), and no side library restates another's arithmetic -- but for the five lines of the
-hash finaliser that augment has in common with maskcrop (each shared header's users are stated by the tests of the libraries before it).
+hash finaliser that augment has in common with maskcrop, and the wave scans that rle writes out for itself (each shared header's users
+are stated by the tests of the libraries before it).
 Every function takes the library it works on as a `Target` (default: the hot-path library)."""
 from __future__ import annotations
 
@@ -87,6 +89,9 @@ _LOADER = (MASKCROP,)
 # the pixel side of the training loader's augmentation (lc_amd.augment); includes no shared header (it restates maskcrop's hash)
 AUGMENT = _side("augment")
 _AUGMENT = (AUGMENT,)
+# the mask store of the training loader (lc_amd.rle); includes no shared header
+RLE = _side("rle")
+_MASK_STORE = (RLE,)
 HASH_MARKER = MAIN.hash_marker
 
 
@@ -128,7 +133,7 @@ def loader_targets():
 def every_target():
     """The ten libraries of the six groups above, in build order.  augment_targets() is NOT among them: the tests of the earlier libraries
     state this tuple, its length and each group member by member, so a library added since is a group beside it; whoever builds
-    everything builds `every_target() + augment_targets()`."""
+    everything builds `every_target() + augment_targets() + mask_store_targets()`."""
     return all_targets() + tool_targets() + eval_targets() + scene_targets() + annot_targets() + loader_targets()
 
 
@@ -136,6 +141,12 @@ def augment_targets():
     """The library behind the training loader's background switch and colour augmentation: built after every_target() by
     `python __graft_entry__.py build`, loaded by no per-step path."""
     return _AUGMENT
+
+
+def mask_store_targets():
+    """The library behind the device-resident store of run-length masks: a group of its own beside every_target() and augment_targets()
+    (the tests of the earlier libraries state both tuples), built last by `python __graft_entry__.py build`."""
+    return _MASK_STORE
 
 
 def sources(target: Target = MAIN):
@@ -289,5 +300,5 @@ def build_variant(name: str, flags, verbose: bool = False) -> str:
 
 
 if __name__ == "__main__":
-    for t in every_target() + augment_targets():
+    for t in every_target() + augment_targets() + mask_store_targets():
         print(build(force=True, verbose=True, target=t))

@@ -1,0 +1,391 @@
+"""The run-length mask store on the device: every output EQUAL to the numpy oracle's (tests/rle_oracle.py) at the shapes of
+tests/rle_cases.py -- one store that mixes the three frame sizes, valid and invalid lists; every window; mask indices; the encoder with
+its cap; bad offsets; a replayed graph; and one chain from rendered annotations through the store into the mask crops."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from tests import rle_cases as cases, rle_oracle as oracle
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+
+
+def _dev(a, dtype=None):
+    return torch.as_tensor(np.asarray(a), dtype=dtype).to(DEV)
+
+
+def _u32(t):
+    return t.cpu().numpy().view(np.uint32)
+
+
+@functools.lru_cache(maxsize=None)
+def _lists():
+    """Every list of every frame: (names, lists, sizes (F,2), frames: the decoded mask or None, valid (F))."""
+    names, lists, sizes, frames = [], [], [], []
+    for H, W in cases.FRAMES:
+        for name, c in cases.valid_lists(H, W):
+            names.append(f"{H}x{W}-{name}"), lists.append(c), sizes.append((H, W)), frames.append(oracle.decode(c, H, W))
+        for name, c in cases.invalid_lists(H, W):
+            names.append(f"{H}x{W}-{name}"), lists.append(c), sizes.append((H, W)), frames.append(None)
+    for m in frames:
+        if m is not None:
+            m.setflags(write=False)
+    valid = np.array([0 if m is not None else -1 for m in frames], dtype=np.int32)
+    return tuple(names), lists, np.asarray(sizes, dtype=np.int32), frames, valid
+
+
+@functools.lru_cache(maxsize=None)
+def _store():
+    from lc_amd import rle
+
+    _, lists, sizes, _, _ = _lists()
+    return rle.RleStore.from_counts(lists, sizes, device=DEV)
+
+
+def test_index_equals_the_oracle_for_every_list():
+    names, lists, sizes, frames, valid = _lists()
+    s = _store()
+    flat = np.concatenate([np.asarray(c, dtype=np.uint32) for c in lists])
+    offsets = np.concatenate(([0], np.cumsum([len(c) for c in lists])))
+    assert s.F == len(lists) and s.T == len(flat) and s.frame_hw is None
+    assert np.array_equal(_u32(s.counts), flat) and np.array_equal(s.offsets.cpu().numpy(), offsets)
+    ends, area, box, v = oracle.index(flat, offsets, sizes)
+    assert np.array_equal(v, valid) and (v == 0).sum() == 3 * 13 and (v == -1).sum() == 3 * 5
+    assert torch.equal(s.valid.cpu(), torch.from_numpy(v))
+    bad = [names[f] for f in range(s.F) if s.area[f].item() != area[f] or s.box[f].cpu().tolist() != box[f].tolist()]
+    assert not bad, bad
+    assert torch.equal(s.area.cpu(), torch.from_numpy(area)) and torch.equal(s.box.cpu(), torch.from_numpy(box))
+    assert np.array_equal(_u32(s.ends), ends)
+    f = names.index("37x53-column-cross")  # a 1-run over a column boundary covers rows 0 and H - 1
+    assert s.box[f].cpu().tolist() == [1, 0, 2, 36] and int(s.area[f]) == 4
+    # the two box conventions and the window origins, plain torch on the device
+    xywh, xywh0 = s.box_xywh().cpu().numpy(), s.box_xywh(plus_one=False).cpu().numpy()
+    for g in range(s.F):
+        x0, y0, x1, y1 = box[g]
+        assert xywh[g].tolist() == ([x0, y0, x1 - x0 + 1, y1 - y0 + 1] if x0 >= 0 else [-1] * 4), names[g]
+        assert xywh0[g].tolist() == ([x0, y0, x1 - x0, y1 - y0] if x0 >= 0 else [-1] * 4), names[g]
+    org = s.window_origins(None, (20, 31)).cpu().numpy()
+    idx = _dev([f, 0, f], torch.int32)
+    assert org.dtype == np.int32 and org[f].tolist() == [(1 + 2 + 1 - 31) // 2, (0 + 36 + 1 - 20) // 2] and org[0].tolist() == [0, 0]
+    assert s.window_origins(idx, (20, 31)).cpu().tolist() == [org[f].tolist(), [0, 0], org[f].tolist()]
+
+
+WINDOWS = [w[0] for w in cases.windows(*cases.FRAMES[0])]
+
+
+@pytest.mark.parametrize("k", range(len(WINDOWS)), ids=WINDOWS)
+def test_decode_equals_the_oracle_in_every_window(k):
+    """One launch over the whole mixed store per window; the window of row b is the k-th of ITS frame size."""
+    from lc_amd import rle
+
+    names, lists, sizes, frames, valid = _lists()
+    s = _store()
+    for H, W in cases.FRAMES:  # the window's size is that of one frame's k-th window; every row gets the origin of its own frame's
+        wname, _, hw = cases.windows(H, W)[k]
+        origins = np.array([cases.windows(int(h), int(w))[k][1] for h, w in sizes], dtype=np.int32)
+        got, info = rle.decode(s, origin_xy=_dev(origins), hw=hw)
+        want, winfo = oracle.decode_rows(frames, valid, s.F, range(s.F), origins, hw)
+        assert got.dtype == torch.uint8 and got.shape == (s.F,) + tuple(hw) and got.is_contiguous()
+        assert torch.equal(info.cpu(), torch.from_numpy(winfo)) and np.array_equal(winfo, valid)
+        bad = [names[f] for f in range(s.F) if not torch.equal(got[f].cpu(), torch.from_numpy(want[f]))]
+        assert not bad, (wname, hw, bad)
+        if wname.startswith("outside"):
+            assert not want.any()
+        elif wname not in ("one-pixel",):
+            assert want.any()
+
+
+def test_decode_without_origins_and_an_origin_beyond_the_bound():
+    from lc_amd import rle
+
+    names, lists, sizes, frames, valid = _lists()
+    s = _store()
+    got, info = rle.decode(s, hw=(64, 64))
+    want, winfo = oracle.decode_rows(frames, valid, s.F, range(s.F), None, (64, 64))
+    assert torch.equal(got.cpu(), torch.from_numpy(want)) and torch.equal(info.cpu(), torch.from_numpy(winfo))
+    f = names.index("64x64-blob")
+    idx = _dev([f] * 6, torch.int32)
+    M = oracle.MAX_ORIGIN
+    origins = np.array([[M, 0], [M + 1, 0], [0, -M - 1], [-M, -M], [2 ** 31 - 1, -2 ** 31], [0, 0]], dtype=np.int64)
+    got, info = rle.decode(s, idx, _dev(origins).to(torch.int32), (9, 65))
+    assert info.cpu().tolist() == [0, -1, -1, 0, -1, 0] and not got[:5].any() and got[5].any()
+    assert torch.equal(got[5].cpu(), torch.from_numpy(oracle.window_of(frames[f], (0, 0), (9, 65))))
+
+
+def test_mask_index_repeated_permuted_out_of_range_and_any_batch():
+    from lc_amd import rle
+
+    names, lists, sizes, frames, valid = _lists()
+    s = _store()
+    rng = np.random.default_rng(3)
+    hw = (41, 70)
+    index = np.concatenate((rng.permutation(s.F), [5, 5, 5, -1, s.F, s.F + 7, -2 ** 31, 2 ** 31 - 1, 0])).astype(np.int32)
+    origins = rng.integers(-12, 30, (len(index), 2)).astype(np.int32)
+    got, info = rle.decode(s, _dev(index), _dev(origins), hw)
+    want, winfo = oracle.decode_rows(frames, valid, s.F, index.tolist(), origins, hw)
+    assert torch.equal(got.cpu(), torch.from_numpy(want)) and torch.equal(info.cpu(), torch.from_numpy(winfo))
+    assert winfo[s.F + 3:s.F + 8].tolist() == [-1] * 5 and want.any()
+    # the same rows in another order and batch size: the same bytes
+    pick = rng.permutation(len(index))[:17]
+    part, pinfo = rle.decode(s, _dev(index[pick]), _dev(origins[pick]), hw)
+    assert torch.equal(part, got[_dev(pick)]) and torch.equal(pinfo, info[_dev(pick)])
+    one, _ = rle.decode(s, _dev(index[3:4]), _dev(origins[3:4]), hw)
+    assert torch.equal(one[0], got[3])
+    # into given tensors, dirty ones
+    out = (torch.full((17,) + hw, 7, dtype=torch.uint8, device=DEV), torch.full((17,), 9, dtype=torch.int32, device=DEV))
+    same = rle.decode(s, _dev(index[pick]), _dev(origins[pick]).long(), hw, out=out)
+    assert same[0] is out[0] and torch.equal(out[0], part) and torch.equal(out[1], pinfo)
+
+
+def test_empty_batch_and_empty_store():
+    from lc_amd import rle
+
+    s = _store()
+    got, info = rle.decode(s, torch.zeros(0, dtype=torch.int32, device=DEV), hw=(5, 6))
+    assert got.shape == (0, 5, 6) and info.shape == (0,)
+    none = rle.RleStore.from_counts([], (5, 6), device=DEV)
+    assert none.F == 0 and none.T == 0 and none.area.shape == (0,) and none.box.shape == (0, 4) and none.to_coco() == []
+    got, info = rle.decode(none, hw=(5, 6))
+    assert got.shape == (0, 5, 6) and info.shape == (0,)
+    got, info = rle.decode(none, _dev([0, 1, -1], torch.int32), hw=(5, 6))  # rows of a store without masks: all refused
+    assert info.cpu().tolist() == [-1, -1, -1] and not got.any()
+    enc = rle.encode(torch.zeros(0, 5, 6, dtype=torch.uint8, device=DEV), cap=4)
+    assert enc.counts.shape == (0, 4) and enc.n_runs.shape == (0,)
+
+
+def test_offsets_that_decrease_or_pass_the_end_are_judged_on_the_device():
+    from lc_amd import rle
+
+    H, W = 37, 53
+    named = dict(cases.valid_lists(H, W))
+    lists = [named["blob"], named["long-run"], named["full"], named["corner-br"], named["checkerboard"]]
+    flat = np.concatenate([np.asarray(c, dtype=np.uint32) for c in lists])
+    good = np.concatenate(([0], np.cumsum([len(c) for c in lists]))).astype(np.int64)
+    T = len(flat)
+    sizes = np.tile(np.array([[H, W]], np.int32), (5, 1))
+    frames = [oracle.decode(c, H, W) for c in lists]
+    for offsets, want_valid in ((np.array([good[0], good[1], good[2], T + 3, good[4], good[5]]), [0, 0, -1, -1, 0]),   # past T, then decreasing
+                                (np.array([-2, good[1], good[2], good[3], good[4], 2 ** 62]), [-1, 0, 0, 0, -1]),     # negative; far past T
+                                (np.array([good[0], good[1], good[2], good[3], good[4], good[5]]), [0] * 5)):
+        s = rle.RleStore(_dev(flat.view(np.int32)), _dev(offsets.astype(np.int64)), _dev(sizes))
+        ends, area, box, valid = oracle.index(flat, offsets, sizes)
+        assert valid.tolist() == want_valid
+        assert torch.equal(s.valid.cpu(), torch.from_numpy(valid)) and torch.equal(s.area.cpu(), torch.from_numpy(area)) and torch.equal(s.box.cpu(), torch.from_numpy(box))
+        assert np.array_equal(_u32(s.ends), ends)  # nothing written for the masks with bad offsets: the zeros the store was made with
+        got, info = rle.decode(s, hw=(H, W))
+        want, winfo = oracle.decode_rows(frames, valid, 5, range(5), None, (H, W))
+        assert torch.equal(got.cpu(), torch.from_numpy(want)) and info.cpu().tolist() == want_valid == winfo.tolist()
+    # a bad size on the device
+    bad_sizes = sizes.copy()
+    bad_sizes[1], bad_sizes[3] = (0, W), (H, 16385)
+    s = rle.RleStore(_dev(flat.view(np.int32)), _dev(good), _dev(bad_sizes))
+    assert s.valid.cpu().tolist() == [0, -1, 0, -1, 0] == oracle.index(flat, good, bad_sizes)[3].tolist()
+    assert rle.decode(s, hw=(H, W))[1].cpu().tolist() == [0, -1, 0, -1, 0]
+
+
+@functools.lru_cache(maxsize=None)
+def _encode_case(k):
+    """The k-th window of every valid mask with bytes other than 1 and garbage where the window leaves the frame, and the oracle's lists."""
+    names, lists, sizes, frames, valid = _lists()
+    rng = np.random.default_rng(100 + k)
+    keep = [f for f in range(len(lists)) if valid[f] == 0]
+    hw = cases.windows(*cases.FRAMES[1])[k][2]
+    origins = np.array([cases.windows(int(sizes[f][0]), int(sizes[f][1]))[k][1] for f in keep], dtype=np.int32)
+    wins = []
+    for f, org in zip(keep, origins):
+        w = oracle.window_of(frames[f], org, hw) * rng.integers(1, 256, hw).astype(np.uint8)
+        inside = oracle.window_of(np.ones(frames[f].shape, np.uint8), org, hw)
+        wins.append(np.where(inside != 0, w, rng.integers(0, 256, hw).astype(np.uint8)))
+    wins = np.stack(wins)
+    need = oracle.encode_rows(wins, sizes[keep], origins, 1)[1]
+    return [names[f] for f in keep], wins, sizes[keep], origins, need
+
+
+@pytest.mark.parametrize("k", range(len(WINDOWS)), ids=WINDOWS)
+def test_encode_equals_the_oracle_in_every_window(k):
+    from lc_amd import rle
+
+    names, wins, sizes, origins, need = _encode_case(k)
+    assert (wins > 1).any()
+    for cap in (int(need.max()), int(need.max()) - 1):  # exactly sufficient, and one short for the masks that need the most
+        if cap < 1:
+            continue
+        enc = rle.encode(_dev(wins), _dev(sizes), _dev(origins), cap)
+        want, n_runs, info = oracle.encode_rows(wins, sizes, origins, cap)
+        assert np.array_equal(n_runs, need) and ((info == -2) == (need > cap)).all() and (info == -2).any() == (cap < need.max())
+        assert torch.equal(enc.n_runs.cpu(), torch.from_numpy(n_runs)) and torch.equal(enc.info.cpu(), torch.from_numpy(info))
+        bad = [names[f] for f in range(len(names)) if not np.array_equal(_u32(enc.counts[f]), want[f])]
+        assert not bad, (WINDOWS[k], cap, bad)
+
+
+def test_encode_of_whole_frames_bool_masks_and_refused_rows():
+    from lc_amd import rle
+
+    names, lists, sizes, frames, valid = _lists()
+    for H, W in cases.FRAMES:
+        keep = [f for f in range(len(lists)) if valid[f] == 0 and tuple(sizes[f]) == (H, W)]
+        masks = np.stack([frames[f] for f in keep])
+        enc = rle.encode(_dev(masks).bool(), cap=H * W + 1)  # no sizes, no origins: the window is the frame
+        want, n_runs, info = oracle.encode_rows(masks, None, None, H * W + 1)
+        assert not info.any() and torch.equal(enc.info.cpu(), torch.from_numpy(info)) and torch.equal(enc.n_runs.cpu(), torch.from_numpy(n_runs))
+        assert np.array_equal(_u32(enc.counts), want)
+        assert n_runs.max() == H * W and n_runs.min() == 1  # the alternating mask, the empty one
+        # the store made from these masks holds the canonical lists, and decodes to the masks
+        s = rle.RleStore.from_masks(_dev(masks), cap=H * W + 1)
+        assert s.frame_hw == (H, W) and not s.valid.any() and torch.equal(rle.decode(s)[0].cpu(), torch.from_numpy(masks))
+        for f, rec in zip(keep, s.to_coco(compress=False)):
+            assert rec == {"size": [H, W], "counts": oracle.encode(frames[f]).tolist()}, names[f]
+        back = rle.RleStore.from_coco(s.to_coco(), device=DEV)  # through the compressed strings
+        assert torch.equal(back.counts, s.counts) and torch.equal(back.offsets, s.offsets) and torch.equal(back.sizes, s.sizes)
+        with pytest.raises(ValueError, match=rf"needs {H * W} runs, more than cap = 64 \(the largest need is {H * W}\)"):
+            rle.RleStore.from_masks(_dev(masks), cap=64)
+    # rows with a size or an origin out of range: -1, no runs, a zero row; their neighbours untouched
+    m = _dev(np.stack([frames[0]] * 4))
+    sz = _dev(np.array([[37, 53], [0, 53], [37, 16385], [37, 53]], np.int32))
+    org = _dev(np.array([[0, 0], [0, 0], [0, 0], [oracle.MAX_ORIGIN + 1, 0]], np.int32))
+    out = (torch.full((4, 8), 7, dtype=torch.int32, device=DEV), torch.full((4,), 7, dtype=torch.int32, device=DEV), torch.full((4,), 7, dtype=torch.int32, device=DEV))
+    enc = rle.encode(m, sz, org, 8, out=out)
+    assert enc.info.cpu().tolist() == [0, -1, -1, -1] and enc.n_runs.cpu().tolist() == [1, 0, 0, 0] and enc.counts.cpu().tolist() == [[37 * 53] + [0] * 7] + [[0] * 8] * 3
+    with pytest.raises(ValueError, match="mask 1 has a frame size or an origin out of range"):
+        rle.RleStore.from_masks(m, sz, org, 8)
+
+
+def test_graph_replay_follows_a_store_overwritten_in_place():
+    from lc_amd import rle
+
+    names, lists, sizes, frames, valid = _lists()
+    F = len(lists)
+    rng = np.random.default_rng(11)
+    hw, cap = (45, 66), 96
+    index = rng.integers(0, F, 24).astype(np.int32)
+    origins = rng.integers(-10, 20, (24, 2)).astype(np.int32)
+
+    def arrays(perm):
+        ls, sz = [lists[f] for f in perm], sizes[perm]
+        return (np.concatenate([np.asarray(c, dtype=np.uint32) for c in ls]), np.concatenate(([0], np.cumsum([len(c) for c in ls]))).astype(np.int64), sz,
+                [frames[f] for f in perm], valid[perm])
+
+    first, second = arrays(np.arange(F)), arrays(rng.permutation(F))
+    wins = [np.stack([oracle.window_of(fr if fr is not None else np.zeros(tuple(sz), np.uint8), (3, -2), hw) for fr, sz in zip(a[3], a[2])]) * 3 for a in (first, second)]
+    s = rle.RleStore(_dev(first[0].view(np.int32)), _dev(first[1]), _dev(first[2]))
+    t = dict(idx=_dev(index), org=_dev(origins), wins=_dev(wins[0]), worg=_dev(np.tile(np.array([[3, -2]], np.int32), (F, 1))))
+    outs = dict(dec=(torch.empty((24,) + hw, dtype=torch.uint8, device=DEV), torch.empty(24, dtype=torch.int32, device=DEV)),
+                enc=tuple(torch.empty(shape, dtype=torch.int32, device=DEV) for shape in ((F, cap), (F,), (F,))))
+
+    def call():
+        s.index()
+        rle.decode(s, t["idx"], t["org"], hw, out=outs["dec"])
+        rle.encode(t["wins"], s.sizes, t["worg"], cap, out=outs["enc"])
+
+    def check(a, w, what):
+        ends, area, box, v = oracle.index(a[0], a[1], a[2])
+        assert np.array_equal(_u32(s.ends), ends) and torch.equal(s.area.cpu(), torch.from_numpy(area)) and torch.equal(s.box.cpu(), torch.from_numpy(box)), what
+        assert torch.equal(s.valid.cpu(), torch.from_numpy(v)) and np.array_equal(v, a[4]), what
+        want, winfo = oracle.decode_rows(a[3], a[4], F, index.tolist(), origins, hw)
+        assert torch.equal(outs["dec"][0].cpu(), torch.from_numpy(want)) and torch.equal(outs["dec"][1].cpu(), torch.from_numpy(winfo)), what
+        counts, n_runs, info = oracle.encode_rows(w, a[2], np.tile(np.array([[3, -2]]), (F, 1)), cap)
+        assert np.array_equal(_u32(outs["enc"][0]), counts) and torch.equal(outs["enc"][1].cpu(), torch.from_numpy(n_runs)) and torch.equal(outs["enc"][2].cpu(), torch.from_numpy(info)), what
+        assert (info == -2).any() and (info == 0).any()
+
+    call()
+    torch.cuda.synchronize()
+    check(first, wins[0], "eager")
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        call()
+    torch.cuda.current_stream().wait_stream(side)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):  # a host synchronisation, an allocation that is read back or a wait in here would fail the capture
+        assert torch.cuda.is_current_stream_capturing()
+        call()
+    s.counts.copy_(_dev(second[0].view(np.int32)))
+    s.offsets.copy_(_dev(second[1]))
+    s.sizes.copy_(_dev(second[2]))
+    t["wins"].copy_(_dev(wins[1]))
+    for o in (*outs["dec"], *outs["enc"], s.area, s.box, s.valid):
+        o.fill_(5)
+    for _ in range(2):
+        g.replay()
+        torch.cuda.synchronize()
+        check(second, wins[1], "replay")
+
+
+def test_chain_from_rendered_annotations_through_the_store_into_the_mask_crops():
+    from lc_amd import gtinfo, maskcrop, render, rle
+    from tests import render_cases as rc
+
+    H, W = 48, 64  # the smallest scene of tests/test_gpu_gtinfo.py: three meshes near the optical axis against a measured depth
+    f = 1.25 * max(H, W)
+    K = _dev(np.array([[f, 0.03 * f, W // 2], [0, 0.97 * f, H // 2], [0, 0, 1]], dtype=np.float32))
+    meshes = render.MeshSet([rc.MESHES[m] for m in ("ico", "torus", "box")], DEV)
+    poses = [rc.POSES[m] for m in ("ico", "torus", "box")]
+    p = dict(mesh_index=torch.tensor((0, 1, 2), dtype=torch.int32, device=DEV), R=_dev(np.stack([q.R for q in poses])), t=_dev(np.stack([q.t for q in poses])))
+    test = np.random.default_rng(5).uniform(0.35, 1.0, size=(1, H, W)).astype(np.float32)
+    test[0, 10:20, 10:30] = 0
+    kw = dict(delta=0.015, near=rc.NEAR, far=rc.FAR)
+    full = gtinfo.compute_gt_info(meshes, p["mesh_index"], p["R"], p["t"], K, _dev(test), **kw)
+    assert full.mask_visib.shape == (3, H, W) and full.mask_visib.any()
+    s = rle.RleStore.from_masks(full.mask_visib)
+    back, info = rle.decode(s, origin_xy=full.origin_xy)
+    assert not info.any() and not s.valid.any() and torch.equal(back, full.mask_visib.to(torch.uint8))
+    assert torch.equal(s.area, full.info[:, gtinfo.PX_VISIB]) and torch.equal(s.box, full.info[:, 8:12])
+    M = _dev(np.array([[[0.6, 0.1, 2.0], [-0.1, 0.6, 5.0]], [[0.5, 0.0, 0.0], [0.0, 0.5, 0.0]], [[0.7, -0.2, 9.0], [0.2, 0.7, -4.0]]], dtype=np.float32))
+    mk = dict(origin=full.origin_xy, valid_th=1, n_check=16, seed=3)
+    a, b = maskcrop.mask_crops(back, M, (32, 32), **mk), maskcrop.mask_crops(full.mask_visib, M, (32, 32), **mk)
+    assert all(torch.equal(x, y) for x, y in zip(a, b)) and int(a.valid_cnt.sum()) > 0
+    # a window per row, one overhanging the frame: the window's part of the frame comes back
+    org = torch.tensor([[20, 10], [0, 0], [W // 2, -3]], dtype=torch.int32, device=DEV)
+    win = gtinfo.compute_gt_info(meshes, p["mesh_index"], p["R"], p["t"], K, _dev(test), window_hw=(30, 28), window_xy=org, **kw)
+    sw = rle.RleStore.from_masks(win.mask_visib, sizes=(H, W), origin_xy=win.origin_xy)
+    got, _ = rle.decode(sw, origin_xy=win.origin_xy, hw=(30, 28))
+    m = win.mask_visib.cpu().numpy().astype(np.uint8)
+    want = np.stack([oracle.window_of(oracle.frame_of(m[r], org[r].tolist(), (H, W)), org[r].tolist(), (30, 28)) for r in range(3)])
+    assert sw.frame_hw == (H, W) and torch.equal(got.cpu(), torch.from_numpy(want)) and want.any()
+    assert torch.equal(sw.area.cpu(), torch.from_numpy(want.reshape(3, -1).sum(1).astype(np.int32)))
+
+
+def test_annotation_tool_writes_the_run_length_records(tmp_path):
+    """`python -m lc_amd.gen_gt_info --rle`: the records decode (by the oracle) to the byte masks the tool writes beside them."""
+    import json
+
+    from lc_amd import gen_gt_info
+    from tests import render_cases as rc
+
+    H, W = 40, 48
+    f = 1.25 * max(H, W)
+    Kn = np.array([[f, 0.03 * f, W // 2], [0, 0.97 * f, H // 2], [0, 0, 1]], dtype=np.float32)
+    models, scene = tmp_path / "models", tmp_path / "000001"
+    models.mkdir()
+    scene.mkdir()
+    for obj_id, m in ((1, "ico"), (4, "torus")):
+        v, faces = rc.MESHES[m]
+        with open(models / f"obj_{obj_id:06d}.ply", "w") as fo:
+            fo.write(f"ply\nformat ascii 1.0\nelement vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\nelement face {len(faces)}\n"
+                     "property list uchar int vertex_indices\nend_header\n")
+            for p in v.astype(np.float64) * 1000.0:
+                fo.write(" ".join(repr(float(x)) for x in p) + "\n")
+            for t in faces:
+                fo.write("3 " + " ".join(str(int(i)) for i in t) + "\n")
+
+    def anno(obj_id, m):
+        p = rc.POSES[m]
+        return dict(obj_id=obj_id, cam_R_m2c=[float(x) for x in p.R.reshape(-1)], cam_t_m2c=[float(x) * 1000.0 for x in p.t])
+
+    gt = {"7": [anno(1, "ico"), anno(4, "torus"), anno(9, "ico")]}  # no model 9: an empty mask keeps its place
+    (scene / "scene_gt.json").write_text(json.dumps(gt))
+    (scene / "scene_camera.json").write_text(json.dumps({"7": dict(cam_K=[float(x) for x in Kn.reshape(-1)], depth_scale=1.0)}))
+    assert gen_gt_info.main([str(scene), str(models), "--frame-hw", str(H), str(W), "--margin", "8", "6", "--rle"]) == 0
+    z = np.load(scene / "mask_npz" / "000007.npz")
+    runs = np.load(scene / "mask_rle.npy", allow_pickle=True).item()
+    assert sorted(runs) == ["mask", "mask_visib"] and z["mask"].any() and z["mask_visib"].any()
+    for key in ("mask", "mask_visib"):
+        assert list(runs[key]) == [f"000007_{i:06d}" for i in range(3)]
+        for i, rec in enumerate(runs[key].values()):
+            assert rec["size"] == [H, W] and isinstance(rec["counts"], bytes)
+            counts = oracle.from_string(rec["counts"])
+            assert counts == oracle.encode(z[key][i]).tolist(), (key, i)
+        assert runs[key]["000007_000002"]["counts"] == oracle.to_string([H * W]).encode()
