@@ -169,3 +169,96 @@ def loader_fixture():
                 cfg_global=types.SimpleNamespace(), np_annots=[(im_info, inst) for inst in insts], model_info=model_info, sym_obj_ids=[],
                 fps=fps, sparse_cnt=3, transform_model=True, training=False, debug=False, valid_pix_cnt_th=100, mask_interp=1,
                 net_input_wh=NET_INPUT_WH, net_output_wh=NET_OUTPUT_WH)
+
+
+# ---- wide crops: the warp launch's layouts beyond 32 threads along x (tests/test_crops_oracle.py, tests/test_gpu_crops.py) ----
+# h = 17 is two bands of 16 rows, the second with one row.  w = 129 and 256 lay the 256 threads out as 64 quads x 4 rows (256: whole
+# quads, vector stores), 257 as 128 x 2, 513 as 256 x 1; 1024 is one full trip of the quad loop, 1025 a second trip with a partial quad,
+# 1028 a second trip with a whole one.  256 x 256 is the workload's size.
+WIDE_SIZES = ((17, 129), (17, 256), (17, 257), (17, 513), (17, 1024), (17, 1025), (17, 1028), (256, 256))
+WIDE_FRAME_INDEX = np.array([1, 0], dtype=np.int32)
+WIDE_MISTAKES = ("x_mod_1024", "row_stride_8")
+THREADS, MIN_BAND = 256, 16
+
+
+def warp_grid(h, w, threads=THREADS, min_band=MIN_BAND):
+    """(band, nbands, lg_tx) of the warp launch, as lc_amd/csrc/shared/lc_warp_grid.h lays it out: 2^lg_tx threads along x, each owning
+    four pixels, and threads >> lg_tx rows per pass."""
+    quads, lg_tx = (w + 3) // 4, 0
+    while (1 << lg_tx) < quads and (1 << lg_tx) < threads:
+        lg_tx += 1
+    band = max(threads >> lg_tx, min_band)
+    return band, (h + band - 1) // band, lg_tx
+
+
+def rows_walked(h, w, stride=None):
+    """(h,) bool: the crop rows that the launch's row loop `for (y = band * grid.band + ty; y < y_end; y += TY)` reaches when it steps
+    by `stride` (None: by TY, and then every row is reached)."""
+    band, nbands, lg_tx = warp_grid(h, w)
+    TY = THREADS >> lg_tx
+    seen = np.zeros(h, dtype=bool)
+    for b in range(nbands):
+        for ty in range(TY):
+            seen[b * band + ty:min(h, (b + 1) * band):stride or TY] = True
+    return seen
+
+
+def stress_matrix(center, frame_hw, out_hw, rot, stretch, skew, cover=1.25, anchor=0.9):
+    """Forward matrix of the suite's `stress` kind (rotation, x stretched, x sheared by y), zoomed so that the crop's longer side spans
+    `cover` frame diagonals.  Frame point `center` goes to the crop point `anchor` of the way along x, half way down: the crop's last
+    columns -- the ones a second trip of the quad loop forms -- read inside the frame, and its first ones far outside it."""
+    c, s = np.cos(rot), np.sin(rot)
+    zoom = max(out_hw) / (cover * np.hypot(*frame_hw))
+    A = np.array([[c, s], [-s, c]]) @ np.array([[stretch, skew], [0.0, 1.0]]) * zoom
+    t = np.array([out_hw[1] * anchor, out_hw[0] * 0.5]) - A @ np.asarray(center, dtype=np.float64)
+    return np.concatenate((A, t[:, None]), axis=1).astype(np.float32)
+
+
+STRESS_KINDS = ((np.deg2rad(25.0), 1.31, 0.23), (np.deg2rad(-50.0), 0.77, -0.4))  # (rot, stretch, skew)
+
+
+def wide_matrices(out_hw):
+    """(2,2,3): one matrix of each stress kind; the crop runs into the frame across one of its corners and ends near its centre."""
+    return np.stack([stress_matrix((W / 2, H / 2), (H, W), out_hw, *kind) for kind in STRESS_KINDS])
+
+
+class planted_coordinates:
+    """Within the block crops_oracle.coordinates carries a mistake of the launch geometry: "x_mod_1024" forms the x terms of column x
+    from x mod 1024 (a thread that keeps its first trip's quad terms on its second trip)."""
+
+    def __init__(self, mistake):
+        self.mistake = mistake
+
+    def __enter__(self):
+        real = self.real = co.coordinates
+        if self.mistake == "x_mod_1024":
+            def wrong(M, out_hw, interp, mistake=None):
+                X, Y = real(M, out_hw, interp, mistake)  # X[y, x] = row term(y) + x term(x) + delta: column x mod 1024 holds the wrong sum
+                cols = np.arange(out_hw[1]) % 1024
+                return X[:, cols], Y[:, cols]
+            co.coordinates = wrong
+
+    def __exit__(self, *exc):
+        co.coordinates = self.real
+
+
+def wide_planted(C, out_hw, interp, mistake):
+    """The oracle's (2,C,h,w) crops of the wide batch under one planted mistake of WIDE_MISTAKES.  "row_stride_8" steps the row loop by 8
+    whatever the layout: the rows it never reaches keep what the buffer held, here 0."""
+    with planted_coordinates(mistake):
+        out, _ = co.warp(FRAMES[C], wide_matrices(out_hw), out_hw, WIDE_FRAME_INDEX, interp)
+    if mistake == "row_stride_8":
+        out[:, :, ~rows_walked(*out_hw, stride=8)] = 0
+    return out
+
+
+def wide_reference(C, out_hw, interp):
+    """(M (2,2,3), out (2,C,h,w) uint8, info (2) int32) of the wide batch from the oracle, computed once per (C, size, interp)."""
+    key = ("wide", C, tuple(out_hw), interp)
+    if key not in _REF:
+        M = wide_matrices(out_hw)
+        out, info = co.warp(FRAMES[C], M, out_hw, WIDE_FRAME_INDEX, interp)
+        out.setflags(write=False)
+        info.setflags(write=False)
+        _REF[key] = (M, out, info)
+    return _REF[key]

@@ -135,3 +135,112 @@ def _warps():
 
 
 WARPS = _warps()
+
+
+# ---- wide crops: the warp launch's layouts beyond 32 threads along x, at the sizes of tests/crops_cases.WIDE_SIZES ----
+def _wide_warps():
+    from tests import crops_cases
+
+    out = []
+    windows = (((33, 47), 10, (6, 9)), ((48, 40), 11, (-20, 15)))  # the windows of "stress-64" and "stress-odd"
+    for hw in crops_cases.WIDE_SIZES:
+        for k, ((mask_hw, seed, origin), kind) in enumerate(zip(windows, crops_cases.STRESS_KINDS)):
+            M = crops_cases.stress_matrix(_centre(mask_hw, origin), mask_hw, hw, *kind)
+            out.append(Warp(f"wide-{hw[0]}x{hw[1]}-{k}", mask_hw, seed, origin, tuple(map(tuple, M.tolist())), hw))
+    return tuple(out)
+
+
+WIDE_WARPS = _wide_warps()
+
+
+def wide_planted(case, vis_interp, mistake):
+    """(msk_vis, msk_noc) of one wide case under a mistake of tests/crops_cases.WIDE_MISTAKES."""
+    from tests import crops_cases
+
+    with crops_cases.planted_coordinates(mistake):
+        vis, noc = maskcrop_oracle.warp_row(mask(case.mask_hw, case.seed), case.origin, case.M, case.out_hw, vis_interp)
+    if mistake == "row_stride_8":  # the rows the loop never reaches keep what the buffer held, here 0
+        skipped = ~crops_cases.rows_walked(*case.out_hw, stride=8)
+        vis[skipped], noc[skipped] = 0, 0
+    return vis, noc
+
+
+# ---- check points: a selection that ends after one, two, three and four passes, and pixels up to p = 65535 ----
+# How many byte passes the device's selection of the n_check smallest keys takes depends only on how many leading key bytes the
+# n_check-th and the (n_check + 1)-th smallest keys share (maskcrop_oracle.selection_depth).  One in a few hundred sample ids shares
+# three bytes on a 256 x 256 crop, one in some ten thousand on a 64 x 64 one, so the rows are searched for, not hoped for.
+DEPTH_SEED = 0xC0FFEE1234567
+DEPTH_N = 256
+# 64 x 64, about 60 % set: the sample ids the search below returns (tests/test_maskcrop_oracle.py runs it for depths 0..2 and
+# re-derives the depth of all four); depth 3 is too rare at this size to be searched for whenever the module is imported
+DEPTH_IDS_64 = {0: 0, 1: 1, 2: 23, 3: 41403}
+
+
+def depth_crop(size):
+    """The (size,size) uint8 crop of the depth rows: 64 -> about 60 % set, 256 -> all set."""
+    return mask((64, 64), 64) if size == 64 else np.ones((size, size), dtype=np.uint8)
+
+
+def boundary_pair(noc, n_check, seed, sample_id):
+    """(depth, p of the n_check-th smallest round-0 key, p of the next): the pair a selection has to part."""
+    p = np.flatnonzero(np.asarray(noc).reshape(-1)).astype(np.int64)
+    k = maskcrop_oracle.key(seed, sample_id, 0, p)
+    at = np.argpartition(k, (n_check - 1, n_check))[n_check - 1:n_check + 1]
+    a, b = int(k[at[0]]), int(k[at[1]])
+    return next((d for d in range(4) if (a >> (24 - 8 * d)) != (b >> (24 - 8 * d))), 4), int(p[at[0]]), int(p[at[1]])
+
+
+def find_depth_ids(noc, depths=(0, 1, 2, 3), tries=4000, n_check=DEPTH_N, seed=DEPTH_SEED):
+    """{depth: the first sample id 0, 1, 2, ... at which the selection is that deep}; a depth-3 row also has the pair's pixels in the
+    order opposite to their keys', so that a selection which stops a byte early and falls back on p takes the wrong pixel.  Raises
+    where `tries` sample ids do not hold every depth asked for."""
+    found = {}
+    for sid in range(tries):
+        d, pa, pb = boundary_pair(noc, n_check, seed, sid)
+        if d in depths and d not in found and (d < 3 or pa > pb):
+            found[d] = sid
+            if len(found) == len(depths):
+                return found
+    raise RuntimeError(f"tests/maskcrop_cases.py: no sample id below {tries} for the selection depths {sorted(set(depths) - set(found))}")
+
+
+_DEPTH_IDS = {}
+
+
+def depth_ids(size):
+    """{depth: sample id} for depths 0..3 on depth_crop(size), found once."""
+    if size not in _DEPTH_IDS:
+        _DEPTH_IDS[size] = dict(DEPTH_IDS_64) if size == 64 else find_depth_ids(depth_crop(size))
+    return _DEPTH_IDS[size]
+
+
+def large_p_masks():
+    """[(name, (256,256) uint8 mask, sample id)]: the pixel index at the width it is packed in, 16 bits.
+    last-300: only the last 300 pixels are set, p = 65236..65535 -- every selected point has bit 15 of p set;
+    last-rows-200: 200 pixels among the last two rows, fewer than the check points -- the rounds path with large p;
+    exactly-256: 256 pixels that include p = 0 and p = 65535 -- the selection takes everything, both ends of the range among it."""
+    n = 256 * 256
+    a = np.zeros(n, dtype=np.uint8)
+    a[n - 300:] = 1
+    b = np.zeros(n, dtype=np.uint8)
+    b[n - 512 + np.random.default_rng(71).permutation(512)[:200]] = 1
+    c = np.zeros(n, dtype=np.uint8)
+    c[1 + np.random.default_rng(72).permutation(n - 2)[:254]] = 1
+    c[0] = c[n - 1] = 1
+    return [("last-300", a.reshape(256, 256), 5), ("last-rows-200", b.reshape(256, 256), 6), ("exactly-256", c.reshape(256, 256), 7)]
+
+
+def planted_points(noc, n_check, seed, sample_id, mistake):
+    """maskcrop_oracle.check_points of a crop with V >= n_check under a mistake of the selection:
+    "top_24_bits": the keys are ordered by their top 24 bits, then by p (a selection that never looks at the last key byte);
+    "p_12_bits": the pixel is taken out of the composite with 12 bits instead of 16."""
+    p = np.flatnonzero(np.asarray(noc).reshape(-1)).astype(np.int64)
+    assert len(p) >= n_check
+    k = maskcrop_oracle.key(seed, sample_id, 0, p)
+    if mistake == "top_24_bits":
+        k = k >> np.uint64(8)
+    q = p[np.lexsort((p, k))][:n_check]
+    if mistake == "p_12_bits":
+        q = q & 0xFFF
+    w = noc.shape[1]
+    return np.stack((q % w, q // w), axis=1)

@@ -101,6 +101,18 @@ def rounds(noc, n_check, seed, sample_id):
     return out
 
 
+def selection_depth(noc, n_check, seed, sample_id):
+    """How deep a selection of the n_check smallest round-0 keys from the top byte down has to look: the number of leading key bytes
+    that the n_check-th and the (n_check + 1)-th smallest keys share, 0..3 (4 if the two keys are equal and only p parts them).  None
+    where there are at most n_check valid pixels: nothing is left out, so there is nothing to select."""
+    p = np.flatnonzero(np.asarray(noc).reshape(-1)).astype(np.int64)
+    if len(p) <= n_check:
+        return None
+    k = np.partition(key(seed, sample_id, 0, p), (n_check - 1, n_check))
+    a, b = int(k[n_check - 1]), int(k[n_check])
+    return next((d for d in range(4) if (a >> (24 - 8 * d)) != (b >> (24 - 8 * d))), 4)
+
+
 def check_points(noc, valid_th, n_check, seed, sample_id):
     """(n_check,2) int64 (x, y)."""
     w = noc.shape[1]

@@ -115,3 +115,42 @@ def test_affine_from_box_is_the_three_point_solve(rot, out_wh):
             zero = np.abs(want) < 1e-12  # entries that are zero but for the solver's rounding (rot = 0)
             ulp = np.where(zero, 1e-12, ulp)
             assert (np.abs(got.astype(np.float64) - want32.astype(np.float64)) <= ulp).all(), (rot, out_wh, center, got, want32)
+
+
+def test_wide_sizes_reach_the_layouts_the_small_sizes_stop_short_of():
+    """The restated launch geometry: the old sizes end at 32 threads along x (lg_tx = 5, eight rows per pass), the wide ones reach 64,
+    128 and 256 threads along x, a second trip of the quad loop, and a second band that holds one row."""
+    assert max(cc.warp_grid(h, w)[2] for h, w in cc.OUT_SIZES) <= 5
+    assert [cc.warp_grid(h, w) for h, w in ((16, 64), (17, 65), (17, 128))] == [(16, 1, 4), (16, 2, 5), (16, 2, 5)]
+    grids = {hw: cc.warp_grid(*hw) for hw in cc.WIDE_SIZES}
+    assert {g[2] for g in grids.values()} == {6, 7, 8}
+    assert [grids[(17, w)][2] for w in (129, 256, 257, 513, 1024, 1025, 1028)] == [6, 6, 7, 8, 8, 8, 8] and grids[(256, 256)] == (16, 16, 6)
+    assert all(g[:2] == (16, 2) for hw, g in grids.items() if hw[0] == 17)
+    quads = sorted((w + 3) // 4 for _, w in cc.WIDE_SIZES)
+    assert quads[-3:] == [256, 257, 257]  # one full trip, and two sizes that need a second
+    assert {w % 4 for _, w in cc.WIDE_SIZES if (w + 3) // 4 > 256} == {0, 1}  # a whole last quad and a partial one
+    for h, w in cc.OUT_SIZES + cc.WIDE_SIZES:
+        assert cc.rows_walked(h, w).all()
+    assert cc.rows_walked(17, 256, stride=8).tolist() == [True] * 4 + [False] * 4 + [True] * 4 + [False] * 4 + [True]
+    assert cc.rows_walked(17, 513, stride=8).sum() == 3 and cc.rows_walked(24, 40, stride=8).all()  # TY >= 8: the mistake cannot show
+
+
+@pytest.mark.parametrize("interp", [co.LINEAR, co.NEAREST])
+@pytest.mark.parametrize("out_hw", cc.WIDE_SIZES)
+@pytest.mark.parametrize("C", [3, 1])
+def test_wide_cases_cross_the_frames_edges_and_notice_a_wrong_layout(C, out_hw, interp):
+    """Every row of every wide case reads pixels inside and outside its frame, and its bytes part from the oracle's under each planted
+    mistake that its layout can show: a row loop that steps by 8 (every wide size has fewer than 8 rows per pass), and x terms formed
+    from x mod 1024 (which is x itself up to w = 1024: only the sizes with a second trip can tell, and they must)."""
+    M, ref, info = cc.wide_reference(C, out_hw, interp)
+    assert not info.any()
+    for b in range(2):
+        X, Y = co.coordinates(M[b], out_hw, co.NEAREST)
+        inside = ((X >> 10) >= 0) & ((X >> 10) < cc.W) & ((Y >> 10) >= 0) & ((Y >> 10) < cc.H)
+        assert inside.any() and not inside.all()
+        sides = [bool(s.any()) for s in ((X >> 10) < 0, (X >> 10) >= cc.W, (Y >> 10) < 0, (Y >> 10) >= cc.H)]  # left, right, top, bottom
+        assert sum(sides) >= 2, sides
+        assert ref[b].any()
+        assert (cc.wide_planted(C, out_hw, interp, "row_stride_8")[b] != ref[b]).any()
+        moved = (cc.wide_planted(C, out_hw, interp, "x_mod_1024")[b] != ref[b])
+        assert moved.any() == (out_hw[1] > 1024) and not moved[..., :1024].any()

@@ -141,6 +141,47 @@ def test_working_shape_four_crops_of_256_from_480x640():
     assert np.array_equal(_bits(got), _bits(torch.from_numpy(want).to(torch.bfloat16)))
 
 
+def _warp_offset(frames, M, hw, dtype, **kw):
+    """warp_affine into a contiguous view that starts ONE element into a sentinel-filled buffer: the pointer is aligned to the element
+    and to no four of them, so the launcher stores element by element at any w.  Asserts the elements around the view, returns the rows."""
+    from lc_amd.crops import warp_affine
+
+    n = M.shape[0] * frames.shape[3] * hw[0] * hw[1]
+    flat = torch.empty(n + 9, device=DEV, dtype=dtype)
+    flat.view(torch.uint8).fill_(SENTINEL)
+    view = flat[1:1 + n].view(M.shape[0], frames.shape[3], *hw)
+    assert view.is_contiguous() and view.data_ptr() % (4 * flat.element_size()) == flat.element_size()
+    out = warp_affine(frames, M, hw, dtype=dtype, out=view, **kw)
+    assert out.data_ptr() == view.data_ptr()
+    guards = torch.cat((flat[:1], flat[1 + n:])).view(torch.uint8)
+    assert bool((guards == SENTINEL).all()), "an element outside the view was written"
+    return out
+
+
+@pytest.mark.parametrize("interp", [co.LINEAR, co.NEAREST])
+@pytest.mark.parametrize("out_hw", cc.WIDE_SIZES, ids=lambda hw: f"{hw[0]}x{hw[1]}")
+@pytest.mark.parametrize("C", [3, 1])
+def test_wide_crops_equal_the_oracle_in_every_thread_layout(C, out_hw, interp):
+    """64, 128 and 256 threads along x, a second trip of the quad loop and the workload's 256 x 256 (tests/crops_cases.WIDE_SIZES), each
+    with four-pixel stores where w allows them and again element by element at an output pointer one element off: the same bytes."""
+    frames, idx = _dev(cc.FRAMES[C]), _dev(cc.WIDE_FRAME_INDEX)
+    M, ref, ref_info = cc.wide_reference(C, out_hw, interp)
+    Md = _dev(M)
+    got, info = _warp_guarded(frames, Md, out_hw, torch.uint8, frame_index=idx, interp=interp)
+    assert got.data_ptr() % 4 == 0 or out_hw[1] % 4, "the guarded rows were meant to take the four-pixel stores"
+    assert np.array_equal(got.cpu().numpy(), ref), int((got.cpu().numpy() != ref).sum())
+    assert np.array_equal(info.cpu().numpy(), ref_info)
+    off = _warp_offset(frames, Md, out_hw, torch.uint8, frame_index=idx, interp=interp)
+    assert np.array_equal(off.cpu().numpy(), ref), int((off.cpu().numpy() != ref).sum())
+    want = co.finish(ref, _norm(C))
+    for dtype in (torch.float32, torch.float16):
+        want_bits = _bits(torch.from_numpy(want).to(dtype))
+        got, _ = _warp_guarded(frames, Md, out_hw, dtype, frame_index=idx, interp=interp, normalize=_norm(C))
+        assert np.array_equal(_bits(got), want_bits), dtype
+        off = _warp_offset(frames, Md, out_hw, dtype, frame_index=idx, interp=interp, normalize=_norm(C))
+        assert np.array_equal(_bits(off), want_bits), dtype
+
+
 def test_finish_blob_gives_the_reference_loaders_rgb_in():
     """The stored blobs of the unmodified reference loader (tests/golden/crops_item.npz, whose warp is the oracle's): collated, moved and
     finished on the device they hold the rgb_in the reference's `.to(float32).div(255)` of the oracle's bytes gives, and not the stand-ins."""

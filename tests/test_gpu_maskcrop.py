@@ -128,6 +128,63 @@ def test_check_points_at_every_count(n_check):
         assert (got.sym_ck_pts2d[0].cpu() == torch.tensor([int(x[0]), int(y[0])])).all() and (got.sym_ck_pts2d[2] == -1).all()
 
 
+def _offset_view(n, shape, dtype, fill):
+    """A contiguous view of `shape` that starts ONE element into a filled buffer (aligned to the element and to no four of them), and the buffer."""
+    flat = torch.full((n + 9,), fill, device=DEV, dtype=dtype)
+    return flat[1:1 + n].view(shape), flat
+
+
+@pytest.mark.parametrize("vis_interp", ["linear", "nearest"])
+@pytest.mark.parametrize("case", cases.WIDE_WARPS, ids=lambda c: c.name)
+def test_wide_crops_equal_the_oracle_in_every_thread_layout(case, vis_interp):
+    """64, 128 and 256 threads along x, a second trip of the quad loop and the workload's 256 x 256 (tests/maskcrop_cases.WIDE_WARPS):
+    msk_vis, msk_noc, valid_cnt and the check points; then into outputs one element off, which the launcher writes element by element
+    at any w: the same bits, and nothing written around them."""
+    window = cases.mask(case.mask_hw, case.seed)
+    h, w = case.out_hw
+    kw = dict(vis_interp=vis_interp, valid_th=1, n_check=16, seed=5)
+    want = oracle.mask_crops(window[None], [case.M], case.out_hw, origin=[case.origin], **kw)
+    got = _run(window[None], [case.M], case.out_hw, origin=[case.origin], **kw)
+    _same(got, want, case.name)
+    assert 0 < got.valid_cnt.item() < h * w
+    assert (got.msk_vis.data_ptr() % 16 == 0 and got.msk_noc.data_ptr() % 4 == 0) or w % 4, "these outputs were meant to take the four-pixel stores"
+    (vis, vis_buf), (noc, noc_buf) = _offset_view(h * w, (1, h, w), torch.float32, 7.0), _offset_view(h * w, (1, h, w), torch.uint8, 9)
+    assert vis.data_ptr() % 16 == 4 and noc.data_ptr() % 4 == 1
+    off = _run(window[None], [case.M], case.out_hw, origin=[case.origin], out=dict(msk_vis=vis, msk_noc=noc), **kw)
+    assert off.msk_vis.data_ptr() == vis.data_ptr() and off.msk_noc.data_ptr() == noc.data_ptr()
+    _same(off, want, case.name + " element by element")
+    assert vis_buf[0].item() == 7.0 and (vis_buf[1 + h * w:] == 7.0).all() and noc_buf[0].item() == 9 and (noc_buf[1 + h * w:] == 9).all()
+
+
+@pytest.mark.parametrize("ck_dtype", [torch.int32, torch.int64])
+@pytest.mark.parametrize("size", [64, 256])
+def test_check_point_selection_at_every_depth_and_at_the_16_bit_limit(size, ck_dtype):
+    """One launch per crop size under the identity: four rows whose selection ends after one, two, three and four byte passes
+    (tests/maskcrop_cases.depth_ids), and at 256 x 256, where p fills its 16 bits, three rows more: only the last 300 pixels set, 200
+    pixels in the last two rows (fewer than the check points: the rounds), and exactly 256 pixels with p = 0 and p = 65535 among them."""
+    ids = cases.depth_ids(size)
+    masks, index, sid = [cases.depth_crop(size)], [0, 0, 0, 0], [ids[d] for d in (0, 1, 2, 3)]
+    if size == 256:
+        for _, m, s in cases.large_p_masks():
+            index.append(len(masks)), masks.append(m), sid.append(s)
+    masks = np.stack(masks)
+    B = len(index)
+    eye = np.tile(np.array(cases.EYE, dtype=np.float32), (B, 1, 1))
+    kw = dict(mask_index=np.array(index, dtype=np.int32), sample_id=np.array(sid, dtype=np.int32), valid_th=VALID_TH, n_check=cases.DEPTH_N, seed=cases.DEPTH_SEED)
+    want = oracle.mask_crops(masks, eye, (size, size), **kw)
+    depths = [oracle.selection_depth(masks[f], cases.DEPTH_N, cases.DEPTH_SEED, s) for f, s in zip(index, sid)]
+    assert depths[:4] == [0, 1, 2, 3] and (size == 64 or (depths[4] in range(4) and depths[5:] == [None, None]))  # None: nothing is left out
+    assert not want["info"].any() and (want["sym_ck_pts2d"] >= 0).all()
+    got = _run(masks, eye, (size, size), ck_dtype=ck_dtype, **kw)
+    assert got.sym_ck_pts2d.dtype == ck_dtype and tuple(got.sym_ck_pts2d.shape) == (B, cases.DEPTH_N, 2)
+    _same(got, want, f"depth rows {size}")
+    if size == 256:
+        assert want["valid_cnt"].tolist() == [size * size] * 4 + [300, 200, 256]
+        p = got.sym_ck_pts2d[:, :, 1].cpu().long() * size + got.sym_ck_pts2d[:, :, 0].cpu().long()
+        assert (p[4] >= 65236).all() and (p[5] >= 254 * 256).all() and p[6].min().item() == 0 and p[6].max().item() == 65535
+        assert (p[:4] >= 4096).any(dim=1).all()
+
+
 def _random_rows(B, seed):
     rng = np.random.default_rng(seed)
     masks = np.stack([cases.mask((40, 44), s) for s in (31, 32, 33, 34, -1)])

@@ -253,6 +253,90 @@ def test_encode_of_whole_frames_bool_masks_and_refused_rows():
         rle.RleStore.from_masks(m, sz, org, 8)
 
 
+WIDE_IDS = [f"{H}x{W}" for H, W in cases.WIDE_FRAMES]
+
+
+@functools.lru_cache(maxsize=None)
+def _wide(HW):
+    """(names, masks (F,H,W) uint8) of one wide frame."""
+    names, masks = zip(*cases.wide_masks(*HW))
+    return names, np.stack(masks)
+
+
+@pytest.mark.parametrize("HW", cases.WIDE_FRAMES, ids=WIDE_IDS)
+def test_encode_joins_its_chunks_of_1024_columns(HW):
+    """Frames of 1030 and 2049 columns (two and three chunks) in every window of tests/rle_cases.wide_windows: the rank and the last
+    boundary carried from chunk to chunk, through a chunk without boundaries, and into a chunk that holds the closing column alone;
+    with a cap that is exactly sufficient and one that is one short."""
+    from lc_amd import rle
+
+    names, masks = _wide(HW)
+    F = len(names)
+    rng = np.random.default_rng(HW[1])
+    for wname, org, hw in cases.wide_windows(*HW):
+        inside = oracle.window_of(np.ones(HW, np.uint8), org, hw) != 0
+        wins = np.stack([np.where(inside, oracle.window_of(m, org, hw) * rng.integers(1, 256, hw).astype(np.uint8), rng.integers(0, 256, hw).astype(np.uint8))
+                         for m in masks])  # bytes other than 1, and garbage where the window leaves the frame
+        sizes, origins = np.tile(np.array([HW], np.int32), (F, 1)), np.tile(np.array([org], np.int32), (F, 1))
+        need = oracle.encode_rows(wins, sizes, origins, 1)[1]
+        assert need.min() == 1 and need.max() > HW[1]
+        for cap in (int(need.max()), int(need.max()) - 1):
+            enc = rle.encode(_dev(wins), _dev(sizes), _dev(origins), cap)
+            want, n_runs, info = oracle.encode_rows(wins, sizes, origins, cap)
+            assert np.array_equal(n_runs, need) and ((info == -2) == (need > cap)).all() and (info == -2).any() == (cap < need.max())
+            assert torch.equal(enc.n_runs.cpu(), torch.from_numpy(n_runs)) and torch.equal(enc.info.cpu(), torch.from_numpy(info)), (wname, cap)
+            bad = [names[f] for f in range(F) if not np.array_equal(_u32(enc.counts[f]), want[f])]
+            assert not bad, (wname, cap, bad)
+
+
+@pytest.mark.parametrize("HW", cases.WIDE_FRAMES, ids=WIDE_IDS)
+def test_wide_store_decodes_and_round_trips(HW):
+    """The store of the wide frames' lists decoded in a window that overhangs the frame all round, five and nine tiles of 256 columns
+    wide; the store made from the masks on the device holds the same lists and comes back from its COCO records."""
+    from lc_amd import rle
+
+    H, W = HW
+    names, masks = _wide(HW)
+    lists = [oracle.encode(m) for m in masks]
+    s = rle.RleStore.from_counts(lists, HW, device=DEV)
+    assert not s.valid.any() and s.frame_hw == HW
+    ends, area, box, valid = oracle.index(np.concatenate(lists), s.offsets.cpu().numpy(), s.sizes.cpu().numpy())
+    assert np.array_equal(_u32(s.ends), ends) and torch.equal(s.area.cpu(), torch.from_numpy(area)) and torch.equal(s.box.cpu(), torch.from_numpy(box))
+    hw = (H + 5, W + 7)
+    assert (hw[1] + 255) // 256 == (5 if W == 1030 else 9)
+    origins = np.tile(np.array([[-3, -2]], np.int32), (s.F, 1))
+    got, info = rle.decode(s, origin_xy=_dev(origins), hw=hw)
+    want, winfo = oracle.decode_rows(list(masks), valid, s.F, range(s.F), origins, hw)
+    assert not winfo.any() and torch.equal(info.cpu(), torch.from_numpy(winfo))
+    bad = [names[f] for f in range(s.F) if not torch.equal(got[f].cpu(), torch.from_numpy(want[f]))]
+    assert not bad, bad
+    made = rle.RleStore.from_masks(_dev(masks), cap=H * W + 1)
+    assert made.frame_hw == HW and torch.equal(made.counts, s.counts) and torch.equal(made.offsets, s.offsets) and not made.valid.any()
+    records = made.to_coco()
+    assert [r["size"] for r in records] == [[H, W]] * s.F and [oracle.from_string(r["counts"]) for r in records] == [c.tolist() for c in lists]
+    back = rle.RleStore.from_coco(records, device=DEV)
+    assert torch.equal(back.counts, s.counts) and torch.equal(back.offsets, s.offsets) and torch.equal(back.sizes, s.sizes)
+    assert torch.equal(rle.decode(back)[0].cpu(), torch.from_numpy(masks))
+
+
+def test_index_carries_64_bits_across_its_chunks_of_256_counts():
+    """Two lists of more than 512 counts: one whose sum is H W only with the carries of all three chunks, and one whose sum passes 2^32
+    in the third chunk and ends at H W + 2^32 -- invalid, though its low 32 bits say H W."""
+    from lc_amd import rle
+
+    H, W = 64, 64
+    (_, good, _), (_, over, _) = cases.chunked_index_lists(H, W)
+    s = rle.RleStore.from_counts([good, over, good], (H, W), device=DEV)
+    flat = np.asarray(good + over + good, dtype=np.uint32)
+    ends, area, box, valid = oracle.index(flat, s.offsets.cpu().numpy(), s.sizes.cpu().numpy())
+    assert valid.tolist() == [0, -1, 0] and ends[len(good) + len(over) - 1] == H * W
+    assert torch.equal(s.valid.cpu(), torch.from_numpy(valid))
+    assert torch.equal(s.area.cpu(), torch.from_numpy(area)) and torch.equal(s.box.cpu(), torch.from_numpy(box))
+    assert np.array_equal(_u32(s.ends), ends)
+    got, info = rle.decode(s)
+    assert info.cpu().tolist() == [0, -1, 0] and not got[1].any() and torch.equal(got[0].cpu(), torch.from_numpy(oracle.decode(good, H, W)))
+
+
 def test_graph_replay_follows_a_store_overwritten_in_place():
     from lc_amd import rle
 

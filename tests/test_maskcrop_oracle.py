@@ -312,3 +312,95 @@ def test_entry_point_checks_its_arguments_before_launching():
     assert call(org=p + 1) != 0 and b"aligned" in msg()
     assert call(noc=None) != 0 and b"workspace is smaller" in msg()
     assert call(cnt=None, ws=p, nbytes=11) != 0 and b"workspace is smaller" in msg()
+
+
+def test_wide_warps_reach_the_layouts_the_small_crops_stop_short_of():
+    """tests/crops_cases.warp_grid restates the launch geometry both libraries share: the crops of WARPS end at 32 threads along x, the
+    wide ones use 64, 128 and 256 and a second trip of the quad loop."""
+    from tests import crops_cases
+
+    assert max(crops_cases.warp_grid(*c.out_hw)[2] for c in cases.WARPS) == 5 and max(c.out_hw[1] for c in cases.WARPS) == 65
+    assert {crops_cases.warp_grid(*c.out_hw)[2] for c in cases.WIDE_WARPS} == {6, 7, 8}
+    assert {c.out_hw for c in cases.WIDE_WARPS} == set(crops_cases.WIDE_SIZES) and len(cases.WIDE_WARPS) == 2 * len(crops_cases.WIDE_SIZES)
+    assert sum((c.out_hw[1] + 3) // 4 > 256 for c in cases.WIDE_WARPS) == 4
+    assert all(c.out_hw[0] * c.out_hw[1] <= oracle.MAX_CHECK_PIXELS for c in cases.WIDE_WARPS)  # check points may be asked for
+
+
+@pytest.mark.parametrize("case", cases.WIDE_WARPS, ids=lambda c: c.name)
+def test_wide_warps_cross_the_windows_edges_and_notice_a_wrong_layout(case):
+    """Every wide case reads inside and outside its window, over at least two of the window's sides, and both of its masks part from
+    the oracle's under a row loop that steps by 8; under x terms formed from x mod 1024 they part exactly where there is a second trip."""
+    window = cases.mask(case.mask_hw, case.seed)
+    X, Y = crops_oracle.coordinates(case.M, case.out_hw, oracle.NEAREST)
+    u, v = (X >> 10) - case.origin[0], (Y >> 10) - case.origin[1]
+    sides = [bool(s.any()) for s in (u < 0, u >= case.mask_hw[1], v < 0, v >= case.mask_hw[0])]
+    assert sum(sides) >= 2, sides
+    for vis_interp in (oracle.LINEAR, oracle.NEAREST):
+        vis, noc = oracle.warp_row(window, case.origin, case.M, case.out_hw, vis_interp)
+        assert 0 < np.count_nonzero(noc) < noc.size
+        if vis_interp == oracle.LINEAR:
+            assert ((vis > 0) & (vis < 1)).any()
+        bad_vis, bad_noc = cases.wide_planted(case, vis_interp, "row_stride_8")
+        assert (bad_vis != vis).any() and (bad_noc != noc).any() and bad_noc.sum() != noc.sum()
+        bad_vis, bad_noc = cases.wide_planted(case, vis_interp, "x_mod_1024")
+        second_trip = case.out_hw[1] > 1024
+        assert (bad_vis != vis).any() == second_trip and (bad_noc != noc).any() == second_trip
+        assert np.array_equal(bad_vis[:, :1024], vis[:, :1024]) and np.array_equal(bad_noc[:, :1024], noc[:, :1024])
+
+
+def test_depth_rows_have_the_depths_they_are_named_for():
+    """The searched sample ids give a selection of every depth 0..3 on both crops; the search is deterministic, and the literal ids of the
+    64 x 64 crop are what it returns (depths 0..2 are searched again here; depth 3 is re-derived, its search takes seconds)."""
+    small, big = cases.depth_crop(64), cases.depth_crop(256)
+    assert small.shape == (64, 64) and 0.55 < small.mean() < 0.65 and big.shape == (256, 256) and big.all()
+    assert cases.find_depth_ids(small, depths=(0, 1, 2), tries=200) == {d: cases.DEPTH_IDS_64[d] for d in (0, 1, 2)}
+    for size, crop in ((64, small), (256, big)):
+        ids = cases.depth_ids(size)
+        assert sorted(ids) == [0, 1, 2, 3] and len(set(ids.values())) == 4
+        for d, sid in ids.items():
+            assert oracle.selection_depth(crop, cases.DEPTH_N, cases.DEPTH_SEED, sid) == d, (size, d, sid)
+            assert cases.boundary_pair(crop, cases.DEPTH_N, cases.DEPTH_SEED, sid)[0] == d
+    assert cases.depth_ids(256) == cases.find_depth_ids(big)
+    assert oracle.selection_depth(cases.noc_with(256, (64, 64), 1), 256, 0, 0) is None and oracle.selection_depth(cases.noc_with(257, (64, 64), 1), 256, 0, 0) in range(4)
+    # the depth is what it says: the two keys share exactly that many leading bytes
+    k = np.sort(oracle.key(cases.DEPTH_SEED, cases.depth_ids(256)[3], 0, np.arange(256 * 256)))
+    assert k[255] >> np.uint64(8) == k[256] >> np.uint64(8) and k[255] != k[256]
+    k = np.sort(oracle.key(cases.DEPTH_SEED, cases.depth_ids(256)[0], 0, np.arange(256 * 256)))
+    assert k[255] >> np.uint64(24) != k[256] >> np.uint64(24)
+
+
+@pytest.mark.parametrize("size", [64, 256])
+def test_depth_3_rows_notice_a_selection_that_skips_the_last_key_byte(size):
+    crop, sid = cases.depth_crop(size), cases.depth_ids(size)[3]
+    good = oracle.check_points(crop, 1, cases.DEPTH_N, cases.DEPTH_SEED, sid)
+    assert np.array_equal(good, cases.planted_points(crop, cases.DEPTH_N, cases.DEPTH_SEED, sid, None))  # the restatement itself
+    bad = cases.planted_points(crop, cases.DEPTH_N, cases.DEPTH_SEED, sid, "top_24_bits")
+    assert not np.array_equal(good, bad)
+    assert {tuple(q) for q in good.tolist()} != {tuple(q) for q in bad.tolist()}  # another pixel is taken, not only another order
+    for d in (0, 1, 2):  # and only there: on the shallower rows the last byte never decides which pixels are taken
+        sid = cases.depth_ids(size)[d]
+        good = oracle.check_points(crop, 1, cases.DEPTH_N, cases.DEPTH_SEED, sid)
+        bad = cases.planted_points(crop, cases.DEPTH_N, cases.DEPTH_SEED, sid, "top_24_bits")
+        assert {tuple(q) for q in good.tolist()} == {tuple(q) for q in bad.tolist()}
+
+
+def test_large_p_masks_hold_the_pixel_index_at_its_full_width():
+    masks = {name: (m, sid) for name, m, sid in cases.large_p_masks()}
+    assert list(masks) == ["last-300", "last-rows-200", "exactly-256"]
+    m, sid = masks["last-300"]
+    p = np.flatnonzero(m.reshape(-1))
+    assert p.tolist() == list(range(65236, 65536)) and (p >> 15).all()
+    good = oracle.check_points(m, 100, cases.DEPTH_N, cases.DEPTH_SEED, sid)
+    assert ((good[:, 1] * 256 + good[:, 0]) >= 65236).all() and len({tuple(q) for q in good.tolist()}) == 256
+    bad = cases.planted_points(m, cases.DEPTH_N, cases.DEPTH_SEED, sid, "p_12_bits")
+    assert not np.array_equal(good, bad) and (good != bad).any(axis=1).all()  # every point moves: each p has bits above the twelfth
+    m, sid = masks["last-rows-200"]
+    p = np.flatnonzero(m.reshape(-1))
+    assert len(p) == 200 and p.min() >= 254 * 256 and oracle.selection_depth(m, cases.DEPTH_N, cases.DEPTH_SEED, sid) is None
+    pts = oracle.check_points(m, 100, cases.DEPTH_N, cases.DEPTH_SEED, sid)
+    assert (pts[:, 1] >= 254).all() and len(oracle.rounds(m, cases.DEPTH_N, cases.DEPTH_SEED, sid)) == 2
+    m, sid = masks["exactly-256"]
+    p = np.flatnonzero(m.reshape(-1))
+    assert len(p) == 256 and p[0] == 0 and p[-1] == 65535 and oracle.selection_depth(m, cases.DEPTH_N, cases.DEPTH_SEED, sid) is None
+    pts = oracle.check_points(m, 100, cases.DEPTH_N, cases.DEPTH_SEED, sid).tolist()
+    assert [0, 0] in pts and [255, 255] in pts

@@ -331,3 +331,60 @@ def test_wrapper_refusals():
         e(m, sizes=(H + 3, W + 3), origin_xy=torch.zeros(2, 2, dtype=torch.int64), cap=4)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         rle.RleStore.from_masks(m)
+
+
+@pytest.mark.parametrize("HW", cases.WIDE_FRAMES, ids=lambda hw: f"{hw[0]}x{hw[1]}")
+def test_wide_frames_notice_an_encoder_that_forgets_the_chunk_before(HW):
+    """The encoder takes 1024 frame columns at a time.  On the wide frames every mask but the empty one has a list that an encoder which
+    restarts its boundary count and its last boundary with each chunk gets wrong, and the masks and windows put a boundary, none at all,
+    and the closing column alone into a later chunk."""
+    H, W = HW
+    assert max(w for _, w in cases.FRAMES) < cases.ENC_CHUNK < W  # the old frames: one chunk, always
+    masks = dict(cases.wide_masks(H, W))
+    assert list(masks)[:6] == ["empty", "full", "blob", "checkerboard", "edge-run", "last-of-1023"] and ("empty-middle" in masks) == (W > 2048)
+    for name, m in masks.items():
+        assert m.shape == (H, W) and m.dtype == np.uint8
+        good = oracle.encode(m).tolist()
+        assert cases.encode_restarting(m, chunk=W + 1) == good  # one chunk: the restatement is the oracle
+        assert (cases.encode_restarting(m) != good) == (name != "empty"), name
+        assert np.array_equal(oracle.decode(good, H, W), m)
+    b = cases.boundaries(masks["edge-run"]) // H
+    assert b.tolist() == [1023, 1024] and oracle.encode(masks["edge-run"]).tolist() == [1024 * H - 1, 2, H * W - 1024 * H - 1]
+    b = cases.boundaries(masks["last-of-1023"]) // H
+    assert b.max() == 1024 and masks["last-of-1023"][H - 1, 1023] and not masks["last-of-1023"][:, 1024:].any()
+    if W > 2048:
+        b = cases.boundaries(masks["empty-middle"]) // H
+        assert ((b < 1024) | (b >= 2048)).all() and (b < 1024).any() and (b >= 2048).sum() >= 2 and masks["empty-middle"][:, 1024:2048].all()
+    # the windows: columns walked, chunks, and where the closing column falls
+    wins = {name: (org, hw) for name, org, hw in cases.wide_windows(H, W)}
+    assert cases.walked_columns(*wins["frame"], HW) == (0, W)
+    assert cases.walked_columns(*wins["closing-alone"], HW) == (0, 1025)  # column 1024 is the only one of chunk two
+    assert cases.walked_columns(*wins["from-6"], HW) == (6, W - 6) and cases.walked_columns(*wins["over-right-bottom"], HW) == (9, W - 9)
+    for wname, (org, hw) in wins.items():
+        xa, ncols = cases.walked_columns(org, hw, HW)
+        differ = []
+        for name, m in masks.items():
+            frame = oracle.frame_of(oracle.window_of(m, org, hw), org, HW)
+            good = oracle.encode(frame).tolist()
+            assert cases.encode_restarting(frame, xa, ncols, chunk=W + 1) == good
+            if cases.encode_restarting(frame, xa, ncols) != good:
+                differ.append(name)
+        assert (len(differ) > 0) == (ncols > cases.ENC_CHUNK), (wname, differ)
+        if wname == "closing-alone":  # the masks with a set pixel at the foot of column 1023 are closed by the lone column
+            assert {"full", "edge-run", "last-of-1023"} <= set(differ)
+
+
+def test_chunked_index_lists_notice_a_32_bit_sum_and_a_dropped_carry():
+    H, W = 64, 64
+    assert all(len(c) <= 4 for _, c in cases.invalid_lists(H, W))  # the old invalid lists: one chunk of 256 counts, always
+    (n1, good, v1), (n2, over, v2) = cases.chunked_index_lists(H, W)
+    assert (n1, v1, n2, v2) == ("carried-sum", True, "carried-overflow", False)
+    assert oracle.is_valid(good, H, W) and not oracle.is_valid(over, H, W)
+    assert len(good) > 2 * cases.IDX_CHUNK and len(over) > 2 * cases.IDX_CHUNK
+    assert cases.valid_with(over, H, W, "sum_32_bits") and cases.valid_with(good, H, W, "sum_32_bits")  # 32 bits take the overflow for valid
+    assert not cases.valid_with(good, H, W, "no_carry") and not cases.valid_with(over, H, W, "no_carry")  # without carries the good list fails
+    assert sum(over[:600]) < 2 ** 32 <= sum(over[:601]) and 600 // cases.IDX_CHUNK == 2  # the sum passes 2^32 in the third chunk
+    flat = np.asarray(good + over, dtype=np.uint32)
+    ends, area, box, valid = oracle.index(flat, [0, len(good), len(good) + len(over)], [(H, W), (H, W)])
+    assert valid.tolist() == [0, -1] and area[0] == sum(good[1::2]) and area[1] == 0 and box[1].tolist() == [-1] * 4
+    assert ends[len(good) - 1] == H * W and ends[-1] == H * W  # the low 32 bits of both sums
