@@ -263,6 +263,18 @@ __device__ __forceinline__ Point load_point(const PnpParams& p, size_t base, int
     return to_point(load_raw_point<OPTS>(p, base, n), cam);
 }
 
+// fmin(fmax(h, 1e-6), 1e32) of a diagonal entry of J^T J, as the two instructions it is.  fmax / fmin must return the other operand for a
+// signalling NaN too, so the compiler puts a canonicalising v_max_f64 h, h in front of them wherever it cannot see where h came from
+// (the totals come back from LDS): six extra issue slots per LM iteration.  h is always the result of an addition or a multiplication
+// -- never a signalling NaN -- and for every other input v_max_f64 / v_min_f64 (IEEE mode, the kernels' default) ARE fmax / fmin:
+// a quiet NaN, -inf, +-0 and anything below 1e-6 give 1e-6, +inf and anything above 1e32 give 1e32, every other value itself.
+__device__ __forceinline__ double clamp_diag(double h) {
+    double lo, r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(lo) : "v"(h), "s"(1e-6));
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(lo), "s"(1e32));
+    return r;
+}
+
 __device__ __forceinline__ double max_abs6(const double (&v)[6]) {
     double m = 0;
 #pragma unroll
@@ -558,16 +570,19 @@ __device__ __forceinline__ void solve_pose(const PnpParams& p, int b, int lane, 
         }
     };
 
-    while (uniform(!failed && !converged)) {
+    // `failed` and `converged` are only ever set on the way out (each assignment below is followed by its break): the loop is entered once
+    // the first evaluation is known to be finite and left by a break -- no ballot over two flags at the head of every iteration.  The
+    // exits are marked unlikely so that an accepted step runs as straight-line code and the others leave it by a taken branch.
+    if (!uniform(failed)) for (;;) {
         // FinalizeIterationAndCheckIfMinimizerCanContinue
-        if (iter >= p.max_iter) break;
-        if (uniform(gmax <= gtol || radius <= 1e-32)) { converged = true; break; }
+        if (__builtin_expect(iter >= p.max_iter, 0)) break;
+        if (__builtin_expect(uniform(gmax <= gtol || radius <= 1e-32), 0)) { converged = true; break; }
         ++iter;
         // LevenbergMarquardtStrategy::ComputeStep on the Jacobi-scaled system
         double dg[6], y[6];
         const double inv_radius = fast_rcp(radius);
 #pragma unroll
-        for (int i = 0; i < 6; ++i) dg[i] = fmin(fmax(H[tri6(i, i)], 1e-6), 1e32) * inv_radius;
+        for (int i = 0; i < 6; ++i) dg[i] = clamp_diag(H[tri6(i, i)]) * inv_radius;
         LC_PSTAMP(1);
         bool step_ok = ldlt_solve6(H, dg, g, y);
         LC_PSTAMP(6);
@@ -577,7 +592,7 @@ __device__ __forceinline__ void solve_pose(const PnpParams& p, int b, int lane, 
         for (int i = 0; i < 6; ++i) mcc += y[i] * (g[i] + dg[i] * y[i]);
         mcc *= 0.5;
         step_ok = step_ok && (mcc > 0.0) && (mcc <= DBL_MAX);  // a non-finite y makes mcc non-finite
-        if (uniform(!step_ok)) {  // HandleInvalidStep
+        if (__builtin_expect(uniform(!step_ok), 0)) {  // HandleInvalidStep
             if (++n_invalid >= 5) { failed = true; trace(0, cost, 0.0, mcc, 0.0, 0.0); break; }
             radius /= dfac; dfac *= 2.0;
             trace(0, cost, 0.0, mcc, 0.0, 0.0);
@@ -594,7 +609,7 @@ __device__ __forceinline__ void solve_pose(const PnpParams& p, int b, int lane, 
         const bool ptol_in_reach = TRACE || uniform(!(sn2 > 2.0 * ptol * ptol * (xn2 + ptol * ptol)));
         double step_norm = 0.0;
         bool ptol_hit = false;
-        if (ptol_in_reach) {  // scalar branch
+        if (__builtin_expect(ptol_in_reach, 0)) {  // scalar branch
             step_norm = fast_sqrt(sn2);
             ptol_hit = uniform(step_norm <= ptol * (fast_sqrt(xn2) + ptol));
         }
@@ -606,15 +621,15 @@ __device__ __forceinline__ void solve_pose(const PnpParams& p, int b, int lane, 
             if (sx->timed_out) { failed = true; break; }
         }
         if (!cand_ok) cost_c = DBL_MAX;
-        if (ptol_hit) {  // ParameterToleranceReached
+        if (__builtin_expect(ptol_hit, 0)) {  // ParameterToleranceReached
             converged = true; trace(3, cost, cost_c, mcc, 0.0, step_norm); break;
         }
         const double cost_change = cost - cost_c;
-        if (uniform(fabs(cost_change) <= ftol * cost)) {    // FunctionToleranceReached
+        if (__builtin_expect(uniform(fabs(cost_change) <= ftol * cost), 0)) {    // FunctionToleranceReached
             converged = true; trace(4, cost, cost_c, mcc, cost_change * fast_rcp(mcc), step_norm); break;
         }
         const double rel = cost_change * fast_rcp(mcc);
-        if (uniform(rel > 1e-3)) {  // HandleSuccessfulStep
+        if (__builtin_expect(uniform(rel > 1e-3), 1)) {  // HandleSuccessfulStep
 #pragma unroll
             for (int j = 0; j < 6; ++j) x[j] = xc[j];
             const double cost_prev = cost;
@@ -629,7 +644,7 @@ __device__ __forceinline__ void solve_pose(const PnpParams& p, int b, int lane, 
             radius /= dfac; dfac *= 2.0;
             trace(2, cost, cost_c, mcc, rel, step_norm);
             double cost_again;
-            if (!evaluate(x, scale, H, g, cost_again)) { failed = true; break; }
+            if (uniform(!evaluate(x, scale, H, g, cost_again))) { failed = true; break; }  // (a ballot like every other exit: one per-lane exit makes the compiler route ALL of them through a flag at the loop's end)
         }
     }
     LC_PSTAMP(1);
