@@ -117,6 +117,27 @@ def load_target(target, signatures, build_if_missing: bool = True):
     return _open(path, signatures)
 
 
+class SideLibrary:
+    """A side library's handle, one per binding module: the whole ctypes table (the three exports every side library has, named after
+    the target, and the module's entry points), the cached `load_target` behind the module's `load()`, and the failure message."""
+
+    def __init__(self, target, entry_points):
+        self.target, self._lib, self._last_error = target, None, f"lc_amd_{target.name}_last_error"
+        self.signatures = {f"lc_amd_{target.name}_version": (c_int, []), self._last_error: (ctypes.c_char_p, []),
+                           f"lc_amd_{target.name}_source_hash": (ctypes.c_char_p, []), **entry_points}
+
+    def load(self, build_if_missing: bool = True):
+        """The library, loaded on first use by `load_target`: one built from other sources than the ones next to it is rebuilt, or refused
+        where hipcc is absent (unless LC_AMD_ALLOW_STALE=1)."""
+        if self._lib is None:
+            self._lib = load_target(self.target, self.signatures, build_if_missing)
+        return self._lib
+
+    def fail(self, what: str, rc: int):
+        """`what`: what the module puts after `lc_amd.` (an entry point's name, or `<module>.<function>`)."""
+        raise RuntimeError(f"lc_amd.{what} failed (code {rc}): {getattr(self.load(), self._last_error)().decode(errors='replace')}")
+
+
 def load(build_if_missing: bool = True):
     """liblc_amd.so, loaded on first use by `load_target`; LC_AMD_LIB names another build of it (a variant), loaded as it is."""
     global _LIB

@@ -30,7 +30,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
 from . import build as _build
 
 MIN_SIZE = 8        # LC_AUGMENT_MIN_SIZE
@@ -61,6 +61,7 @@ DROPOUT_P = 0.1     # iaa.CoarseDropout(p=0.1, size_percent=0.05)
 DROPOUT_PERCENT = 5
 
 _M32 = np.uint64(0xFFFFFFFF)
+_FLOATS = ctypes.POINTER(ctypes.c_float)
 
 
 @dataclass(frozen=True)
@@ -145,9 +146,9 @@ def draw(cfg: AugmentConfig, seed, sample_ids, n_backgrounds, hw=(256, 256)):
     are nested as in the reference: the switch by `switch_bg_prob` (never without backgrounds), the whole colour chain by
     `pixel_aug_prob`, each augmenter by its own `Sometimes` probability (`dataset.py:153-170`).  A row depends on (cfg, seed, its
     sample id, n_backgrounds, hw) alone.  `hw` sizes the dropout grid (5 % of the crop, at least one cell)."""
-    seed = _whole("seed", seed, 0, 2 ** 64 - 1)
-    n_backgrounds = _whole("n_backgrounds", n_backgrounds, 0, 2 ** 31 - 1)
-    h, w = _whole("hw", hw[0], MIN_SIZE, MAX_SIZE), _whole("hw", hw[1], MIN_SIZE, MAX_SIZE)
+    seed = _A.whole("seed", seed, 0, 2 ** 64 - 1, numpy=True)
+    n_backgrounds = _A.whole("n_backgrounds", n_backgrounds, 0, 2 ** 31 - 1, numpy=True)
+    h, w = _A.whole("hw", hw[0], MIN_SIZE, MAX_SIZE, numpy=True), _A.whole("hw", hw[1], MIN_SIZE, MAX_SIZE, numpy=True)
     ids = np.asarray(sample_ids, dtype=np.int64).reshape(-1)
     B = len(ids)
     params = np.zeros((B, WORDS), dtype=np.int32)
@@ -260,49 +261,11 @@ def draw_zoom(cfg: AugmentConfig, seed, sample_ids, bbox_xyxy, im_hw):
     return centre, scale, rot
 
 
-_LIB = None
-_FLOATS = ctypes.POINTER(ctypes.c_float)
-_SIGNATURES = {
-    "lc_amd_augment_version": (c_int, []),
-    "lc_amd_augment_last_error": (ctypes.c_char_p, []),
-    "lc_amd_augment_source_hash": (ctypes.c_char_p, []),
+_SO = _lib.SideLibrary(_build.AUGMENT, {
     "lc_augment_u8": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 3 + [c_int] * 3 + [c_uint64, c_void_p, c_int, c_int, _FLOATS, _FLOATS] + [c_void_p] * 3),
-}
-
-
-def load(build_if_missing: bool = True):
-    """liblc_amd_augment.so, loaded on first use by `_lib.load_target`: a library built from other sources than the ones next to it is
-    rebuilt, or refused where hipcc is absent (unless LC_AMD_ALLOW_STALE=1)."""
-    global _LIB
-    if _LIB is None:
-        _LIB = _lib.load_target(_build.AUGMENT, _SIGNATURES, build_if_missing)
-    return _LIB
-
-
-def _tensor(name, t, dtypes, what, shape):
-    """Type, element type and shape (None: any size)."""
-    if not isinstance(t, Tensor):
-        raise TypeError(f"lc_amd.augment: {name} must be a torch.Tensor, got {type(t)}")
-    if t.dtype not in dtypes:
-        raise TypeError(f"lc_amd.augment: {name} must be {what}, got {t.dtype}")
-    if t.dim() != len(shape) or any(want is not None and have != want for have, want in zip(t.shape, shape)):
-        raise ValueError(f"lc_amd.augment: {name} has shape {tuple(t.shape)}, expected ({', '.join('*' if d is None else str(d) for d in shape)})")
-    return t
-
-
-def _whole(name, v, lo, hi):
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-        raise TypeError(f"lc_amd.augment: {name} must be a whole number, got {type(v)}")
-    if not (lo <= v <= hi):
-        raise ValueError(f"lc_amd.augment: {name} of {lo} to {hi}, got {v}")
-    return int(v)
-
-
-def _host_floats(name, x):
-    vals = [float(v) for v in (x.detach().cpu().reshape(-1).tolist() if isinstance(x, Tensor) else np.asarray(x, dtype=np.float64).reshape(-1))]
-    if len(vals) != 3:
-        raise ValueError(f"lc_amd.augment: normalize {name} must hold one value per channel (3), got {len(vals)}")
-    return (ctypes.c_float * 3)(*vals)
+})
+_SIGNATURES, load = _SO.signatures, _SO.load
+_A = _args.Args("augment")  # its whole numbers may be numpy's (`whole(..., numpy=True)`): seeds and sizes come out of arrays here
 
 
 def check_params(params, h, w, n_backgrounds, has_mask):
@@ -343,7 +306,7 @@ def augment(crops, params, lut, *, msk_in=None, backgrounds=None, seed=0, sample
 
     `pointwise` selects the compiled form that streams without a halo and refuses rows with a filter bit: None takes it when HOST params
     show no row with a filter (device params are not read back: the filtered form serves every row), True / False say it outright."""
-    crops = _tensor("crops", crops, (torch.uint8,), "uint8", (None, 3, None, None))
+    crops = _A.tensor("crops", crops, (torch.uint8,), "uint8", (None, 3, None, None))
     B, _, h, w = (int(s) for s in crops.shape)
     if not (MIN_SIZE <= h <= MAX_SIZE and MIN_SIZE <= w <= MAX_SIZE):
         raise ValueError(f"lc_amd.augment: crop sizes of {MIN_SIZE} to {MAX_SIZE}, got {h} x {w}")
@@ -352,15 +315,15 @@ def augment(crops, params, lut, *, msk_in=None, backgrounds=None, seed=0, sample
         params = torch.from_numpy(np.ascontiguousarray(params))
     if isinstance(lut, np.ndarray):
         lut = torch.from_numpy(np.ascontiguousarray(lut))
-    params = _tensor("params", params, (torch.int32,), "int32", (B, WORDS))
-    lut = _tensor("lut", lut, (torch.uint8,), "uint8", (B, 3, 256))
+    params = _A.tensor("params", params, (torch.int32,), "int32", (B, WORDS))
+    lut = _A.tensor("lut", lut, (torch.uint8,), "uint8", (B, 3, 256))
     if msk_in is not None:
-        _tensor("msk_in", msk_in, (torch.float32,), "float32", (B, h, w))
+        _A.tensor("msk_in", msk_in, (torch.float32,), "float32", (B, h, w))
     if backgrounds is not None:
-        _tensor("backgrounds", backgrounds, (torch.uint8,), "uint8", (None, 3, h, w))
+        _A.tensor("backgrounds", backgrounds, (torch.uint8,), "uint8", (None, 3, h, w))
     if sample_id is not None:
-        _tensor("sample_id", sample_id, (torch.int32,), "int32", (B,))
-    seed = _whole("seed", seed, 0, 2 ** 64 - 1)
+        _A.tensor("sample_id", sample_id, (torch.int32,), "int32", (B,))
+    seed = _A.whole("seed", seed, 0, 2 ** 64 - 1, numpy=True)
     if dtype not in OUT_DTYPES:
         raise TypeError(f"lc_amd.augment: dtype must be one of uint8, float32, float16, bfloat16, got {dtype}")
     if pointwise is not None and not isinstance(pointwise, bool):
@@ -369,7 +332,7 @@ def augment(crops, params, lut, *, msk_in=None, backgrounds=None, seed=0, sample
     if normalize is not None:
         if dtype == torch.uint8:
             raise TypeError("lc_amd.augment: normalize needs a float dtype")
-        mean, std = _host_floats("mean", normalize[0]), _host_floats("std", normalize[1])
+        mean, std = _A.host_floats("mean", normalize[0], 3), _A.host_floats("std", normalize[1], 3)
     G = 0 if backgrounds is None else int(backgrounds.shape[0])
     if host_params:
         filtered = check_params(params.numpy(), h, w, G, msk_in is not None)
@@ -384,9 +347,7 @@ def augment(crops, params, lut, *, msk_in=None, backgrounds=None, seed=0, sample
         params = params.to(dev)
     if not lut.is_cuda:
         lut = lut.to(dev)
-    for name, t in (("params", params), ("lut", lut), ("msk_in", msk_in), ("backgrounds", backgrounds), ("sample_id", sample_id)):
-        if t is not None and t.device != dev:
-            raise RuntimeError(f"lc_amd.augment: {name} is on {t.device}, the crops on {dev}")
+    _A.same_device(dev, "the crops on {}", params=params, lut=lut, msk_in=msk_in, backgrounds=backgrounds, sample_id=sample_id)
     crops, params, lut = crops.contiguous(), params.contiguous(), lut.contiguous()
     msk = None if msk_in is None else msk_in.contiguous()
     bg = None if backgrounds is None or G == 0 else backgrounds.contiguous()
@@ -400,5 +361,5 @@ def augment(crops, params, lut, *, msk_in=None, backgrounds=None, seed=0, sample
                                    _lib.ptr(sid), OUT_DTYPES[dtype], FORMS["pointwise" if pointwise else "filtered"], mean, std, _lib.ptr(out),
                                    _lib.ptr(info), _lib.stream_ptr(dev))
         if rc != 0:
-            raise RuntimeError(f"lc_amd.augment.augment failed (code {rc}): {lib.lc_amd_augment_last_error().decode(errors='replace')}")
+            _SO.fail("augment.augment", rc)
     return out, info

@@ -17,9 +17,9 @@
 A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`): code that
 two libraries need exists once there (lc_shared.h: main, posecov, models, symerr; lc_warp_grid.h: crop, maskcrop; lc_ray_length.h: vsd,
 gtinfo; lc_wave_int.h: vsd, gtinfo, maskcrop), and no side library restates another's arithmetic -- but for the five lines of the
-hash finaliser that augment has in common with maskcrop, and the wave scans that rle writes out for itself (each shared header's users
-are stated by the tests of the libraries before it).
-Every function takes the library it works on as a `Target` (default: the hot-path library)."""
+integer hash finaliser of the device's random numbers that augment has in common with maskcrop, and the wave scans that rle writes out
+for itself (tests/test_posecov_host.py states each shared header's users).
+`TARGETS` is every library in build order.  Every function takes the library it works on as a `Target` (default: the hot-path library)."""
 from __future__ import annotations
 
 import glob
@@ -67,86 +67,26 @@ def _side(name: str, shared: tuple = ()) -> Target:
                   f"LC_AMD_{name.upper()}_SRC_HASH:".encode(), shared)
 
 
-MAIN = Target("main", CSRC, "lc_amd.h", SO_PATH, b"LC_AMD_SRC_HASH:", (SHARED_H,))  # the library carries the hash of its own sources (lc_capi.hip: lc_amd_source_hash)
-OPTIM = _side("optim")
-POSECOV = _side("posecov", (SHARED_H,))
-RENDER = _side("render")
-CROP = _side("crop", (WARP_GRID_H,))
-MODELS = _side("models", (SHARED_H,))  # the offline model preparation (lc_amd.models, python -m lc_amd.prep_models)
-# the evaluation side (lc_amd.metrics.compute_sym_pose_errors): its table rules are those of the label kernels, stated once in lc_sym_args.h
+MAIN = Target("main", CSRC, "lc_amd.h", SO_PATH, b"LC_AMD_SRC_HASH:", (SHARED_H,))  # the hot path of training and test time; carries the hash of its own sources (lc_capi.hip: lc_amd_source_hash)
+OPTIM = _side("optim")  # the fused optimizer step (lc_amd.optim)
+POSECOV = _side("posecov", (SHARED_H,))  # the test-time pose covariance (lc_amd.posecov)
+RENDER = _side("render")  # the depth rasteriser (lc_amd.render)
+CROP = _side("crop", (WARP_GRID_H,))  # the zoom-in crops (lc_amd.crops)
+MODELS = _side("models", (SHARED_H,))  # the offline model preparation (lc_amd.models, python -m lc_amd.prep_models); loaded by no training or test-time path
+# the symmetry-aware evaluation errors (lc_amd.metrics.compute_sym_pose_errors): its table rules are those of the label kernels, stated once in lc_sym_args.h
 SYMERR = _side("symerr", (SHARED_H, os.path.join(CSRC, "lc_sym_args.h")))
-VSD = _side("vsd", (RAY_LENGTH_H, WAVE_INT_H))  # the evaluation error that reads the scene's depth (lc_amd.vsd)
-# the annotation side (lc_amd.gtinfo, python -m lc_amd.gen_gt_info); shares the ray length with VSD
+VSD = _side("vsd", (RAY_LENGTH_H, WAVE_INT_H))  # the evaluation error that reads the scene's measured depth (lc_amd.vsd)
+# the dataset annotations: visibility records, composed scene depth (lc_amd.gtinfo, python -m lc_amd.gen_gt_info); shares the ray length with VSD
 GTINFO = _side("gtinfo", (RAY_LENGTH_H, WAVE_INT_H))
-# the loader side of training (lc_amd.maskcrop); shares the coordinates with CROP
+# the training loader's per-instance mask crops (lc_amd.maskcrop); shares the coordinates with CROP
 MASKCROP = _side("maskcrop", (WARP_GRID_H, WAVE_INT_H))
-_ALL = (MAIN, OPTIM, POSECOV, RENDER, CROP)
-_TOOLS = (MODELS,)
-_EVAL = (SYMERR,)
-_SCENE = (VSD,)
-_ANNOT = (GTINFO,)
-_LOADER = (MASKCROP,)
-# the pixel side of the training loader's augmentation (lc_amd.augment); includes no shared header (it restates maskcrop's hash)
+# the training loader's background switch and colour augmentation (lc_amd.augment); includes no shared header: its device code writes out
+# the same five-line integer hash finaliser as maskcrop's (the per-pixel random numbers; nothing to do with source_hash)
 AUGMENT = _side("augment")
-_AUGMENT = (AUGMENT,)
-# the mask store of the training loader (lc_amd.rle); includes no shared header
-RLE = _side("rle")
-_MASK_STORE = (RLE,)
+RLE = _side("rle")  # the training loader's device-resident store of run-length masks (lc_amd.rle); includes no shared header
+# every library, in build order: whoever builds, hashes or compares "all of them" iterates this
+TARGETS = (MAIN, OPTIM, POSECOV, RENDER, CROP, MODELS, SYMERR, VSD, GTINFO, MASKCROP, AUGMENT, RLE)
 HASH_MARKER = MAIN.hash_marker
-
-
-def all_targets():
-    """Every library of the training and test-time paths, in build order."""
-    return _ALL
-
-
-def tool_targets():
-    """The libraries behind the offline tools: built along with all_targets() by `python __graft_entry__.py build`, loaded by no training
-    or test-time path."""
-    return _TOOLS
-
-
-def eval_targets():
-    """The libraries behind the evaluation metrics that are no part of the training and test-time paths: built along with all_targets() by
-    `python __graft_entry__.py build`."""
-    return _EVAL
-
-
-def scene_targets():
-    """The libraries behind the evaluation metrics that read the scene's measured depth: built along with all_targets() by
-    `python __graft_entry__.py build`."""
-    return _SCENE
-
-
-def annot_targets():
-    """The libraries behind the dataset annotations (visibility records, composed scene depth): built along with all_targets() by
-    `python __graft_entry__.py build`, loaded by no training or test-time path."""
-    return _ANNOT
-
-
-def loader_targets():
-    """The libraries behind the training loader's per-instance work that is no part of the per-step paths: built along with all_targets() by
-    `python __graft_entry__.py build`."""
-    return _LOADER
-
-
-def every_target():
-    """The ten libraries of the six groups above, in build order.  augment_targets() is NOT among them: the tests of the earlier libraries
-    state this tuple, its length and each group member by member, so a library added since is a group beside it; whoever builds
-    everything builds `every_target() + augment_targets() + mask_store_targets()`."""
-    return all_targets() + tool_targets() + eval_targets() + scene_targets() + annot_targets() + loader_targets()
-
-
-def augment_targets():
-    """The library behind the training loader's background switch and colour augmentation: built after every_target() by
-    `python __graft_entry__.py build`, loaded by no per-step path."""
-    return _AUGMENT
-
-
-def mask_store_targets():
-    """The library behind the device-resident store of run-length masks: a group of its own beside every_target() and augment_targets()
-    (the tests of the earlier libraries state both tuples), built last by `python __graft_entry__.py build`."""
-    return _MASK_STORE
 
 
 def sources(target: Target = MAIN):
@@ -300,5 +240,5 @@ def build_variant(name: str, flags, verbose: bool = False) -> str:
 
 
 if __name__ == "__main__":
-    for t in every_target() + augment_targets() + mask_store_targets():
+    for t in TARGETS:
         print(build(force=True, verbose=True, target=t))

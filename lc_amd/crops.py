@@ -26,7 +26,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
 from . import build as _build
 
 logger = logging.getLogger(__name__)
@@ -35,23 +35,12 @@ MAX_SIZE = 16384  # LC_CROP_MAX_SIZE
 INTERP = {"nearest": 0, "linear": 1}  # LC_CROP_NEAREST / LC_CROP_LINEAR
 OUT_DTYPES = {torch.uint8: 0, torch.float32: 1, torch.float16: 2, torch.bfloat16: 3}  # LC_CROP_U8 / _F32 / _F16 / _BF16
 
-_LIB = None
 _FLOATS = ctypes.POINTER(ctypes.c_float)
-_SIGNATURES = {
-    "lc_amd_crop_version": (c_int, []),
-    "lc_amd_crop_last_error": (ctypes.c_char_p, []),
-    "lc_amd_crop_source_hash": (ctypes.c_char_p, []),
+_SO = _lib.SideLibrary(_build.CROP, {
     "lc_crop_warp_u8": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p] + [c_int] * 5 + [_FLOATS, _FLOATS, c_void_p, c_void_p, c_void_p]),
-}
-
-
-def load(build_if_missing: bool = True):
-    """liblc_amd_crop.so, loaded on first use by `_lib.load_target`: a library built from other sources than the ones next to it is
-    rebuilt, or refused where hipcc is absent (unless LC_AMD_ALLOW_STALE=1)."""
-    global _LIB
-    if _LIB is None:
-        _LIB = _lib.load_target(_build.CROP, _SIGNATURES, build_if_missing)
-    return _LIB
+})
+_SIGNATURES, load = _SO.signatures, _SO.load
+_A = _args.Args("crops")
 
 
 def _require(name, t, dtype, what):
@@ -65,13 +54,6 @@ def _require(name, t, dtype, what):
     if not t.is_contiguous():
         raise ValueError(f"lc_amd.crops: {name} must be contiguous, got strides {tuple(t.stride())} for shape {tuple(t.shape)}")
     return t
-
-
-def _host_floats(name, x, C):
-    vals = [float(v) for v in (x.detach().cpu().reshape(-1).tolist() if isinstance(x, Tensor) else np.asarray(x, dtype=np.float64).reshape(-1))]
-    if len(vals) != C:
-        raise ValueError(f"lc_amd.crops: normalize {name} must hold one value per channel ({C}), got {len(vals)}")
-    return (ctypes.c_float * C)(*vals)
 
 
 @torch.no_grad()
@@ -107,7 +89,7 @@ def warp_affine(frames, M, out_hw, *, frame_index=None, interp="linear", normali
     if normalize is not None:
         if dtype == torch.uint8:
             raise TypeError("lc_amd.crops: normalize needs a float dtype")
-        mean, std = _host_floats("mean", normalize[0], C), _host_floats("std", normalize[1], C)
+        mean, std = _A.host_floats("mean", normalize[0], C), _A.host_floats("std", normalize[1], C)
     if out is None:
         out = torch.empty(B, C, h, w, device=dev, dtype=dtype)
     else:
@@ -120,15 +102,13 @@ def warp_affine(frames, M, out_hw, *, frame_index=None, interp="linear", normali
         info = _require("info", info, torch.int32, "int32")
         if tuple(info.shape) != (B,):
             raise ValueError(f"lc_amd.crops: info must be ({B},), got {tuple(info.shape)}")
-    for name, x in (("M", M), ("frame_index", frame_index), ("out", out), ("info", info)):
-        if x is not None and x.device != dev:
-            raise RuntimeError(f"lc_amd.crops: {name} is on {x.device}, the frames on {dev}")
+    _A.same_device(dev, "the frames on {}", M=M, frame_index=frame_index, out=out, info=info)
     lib = load()
     with _lib.on_device(dev):
         rc = lib.lc_crop_warp_u8(_lib.ptr(frames), F, H, W, C, _lib.ptr(frame_index), _lib.ptr(M), B, h, w, INTERP[interp], OUT_DTYPES[dtype],
                                  mean, std, _lib.ptr(out), _lib.ptr(info), _lib.stream_ptr(dev))
     if rc != 0:
-        raise RuntimeError(f"lc_amd.crops.warp_affine failed (code {rc}): {lib.lc_amd_crop_last_error().decode(errors='replace')}")
+        _SO.fail("crops.warp_affine", rc)
     return out
 
 

@@ -29,15 +29,13 @@ allocates its outputs and the composition's workspace only and can be captured i
 """
 from __future__ import annotations
 
-import ctypes
-import math
 from ctypes import c_float, c_int, c_size_t, c_void_p
 from typing import NamedTuple, Optional
 
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
 from . import build as _build
 
 COLUMNS = 12             # LC_GTINFO_COLUMNS
@@ -81,100 +79,22 @@ def _visib_fract(info: Tensor) -> Tensor:
     return torch.where(info[:, PX_ALL] > 0, n_vis / n_all.clamp(min=1.0), torch.zeros_like(n_all))
 
 
-_LIB = None
-_SIGNATURES = {
-    "lc_amd_gtinfo_version": (c_int, []),
-    "lc_amd_gtinfo_last_error": (ctypes.c_char_p, []),
-    "lc_amd_gtinfo_source_hash": (ctypes.c_char_p, []),
+_SO = _lib.SideLibrary(_build.GTINFO, {
     "lc_gtinfo_f32": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_float] * 3 + [c_void_p] * 3),
     "lc_scene_compose_workspace_bytes": (c_size_t, [c_int] * 3),
     "lc_scene_compose_f32": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 4 + [c_size_t, c_void_p]),
-}
-
-
-def load(build_if_missing: bool = True):
-    """liblc_amd_gtinfo.so, loaded on first use by `_lib.load_target`: a library built from other sources than the ones next to it is
-    rebuilt, or refused where hipcc is absent (unless LC_AMD_ALLOW_STALE=1)."""
-    global _LIB
-    if _LIB is None:
-        _LIB = _lib.load_target(_build.GTINFO, _SIGNATURES, build_if_missing)
-    return _LIB
-
-
-def _f32(name: str, t, shape) -> Tensor:
-    """Type, element type and shape (None: any size)."""
-    if not isinstance(t, Tensor):
-        raise TypeError(f"lc_amd.gtinfo: {name} must be a torch.Tensor, got {type(t)}")
-    if t.dtype != torch.float32:
-        raise TypeError(f"lc_amd.gtinfo: {name} must be float32, got {t.dtype}")
-    if t.dim() != len(shape) or any(want is not None and have != want for have, want in zip(t.shape, shape)):
-        raise ValueError(f"lc_amd.gtinfo: {name} has shape {tuple(t.shape)}, expected ({', '.join('*' if d is None else str(d) for d in shape)})")
-    return t
-
-
-def _i32(name: str, t, shape) -> Tensor:
-    if not isinstance(t, Tensor):
-        raise TypeError(f"lc_amd.gtinfo: {name} must be a torch.Tensor, got {type(t)}")
-    if t.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"lc_amd.gtinfo: {name} must be int32 or int64, got {t.dtype}")
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"lc_amd.gtinfo: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
-    return t
-
-
-def _delta(delta) -> float:
-    if isinstance(delta, bool) or not isinstance(delta, (int, float)):
-        raise TypeError(f"lc_amd.gtinfo: delta must be a number, got {type(delta)}")
-    if not math.isfinite(delta) or delta < 0:
-        raise ValueError(f"lc_amd.gtinfo: delta must be finite and not negative, got {delta}")
-    return float(delta)
-
-
-def _pair(name: str, v):
-    if isinstance(v, (Tensor, str)) or not hasattr(v, "__len__") or len(v) != 2:
-        raise ValueError(f"lc_amd.gtinfo: {name} is a pair, got {v!r}")
-    return v[0], v[1]
-
-
-def _center(pixel_center):
-    cx, cy = _pair("pixel_center", pixel_center)
-    return float(cx), float(cy)
+})
+_SIGNATURES, load = _SO.signatures, _SO.load
+_A = _args.Args("gtinfo")
 
 
 def _size(name: str, hw, limit: int):
-    h, w = _pair(name, hw)
+    h, w = _A.pair(name, hw)
     if isinstance(h, bool) or isinstance(w, bool) or not isinstance(h, int) or not isinstance(w, int):
         raise TypeError(f"lc_amd.gtinfo: {name} holds two whole numbers, got {hw!r}")
     if not (1 <= h <= limit and 1 <= w <= limit):
         raise ValueError(f"lc_amd.gtinfo: {name} of 1 to {limit}, got {h} x {w}")
     return h, w
-
-
-def _on(dev, first: str, **named):
-    for name, t in named.items():
-        if t is not None and t.device != dev:
-            raise RuntimeError(f"lc_amd.gtinfo: {name} is on {t.device}, {first} is on {dev}")
-
-
-def _scenes(depth_test, scene_index, B: int):
-    """depth_test as (S,H,W) and the rule for a missing scene_index (that of lc_amd.vsd): one scene serves every instance, B scenes serve
-    one instance each."""
-    if isinstance(depth_test, Tensor) and depth_test.dim() == 2:
-        depth_test = depth_test[None]
-    Dt = _f32("depth_test", depth_test, (None, None, None))
-    S = int(Dt.shape[0])
-    if scene_index is None:
-        if S not in (1, B):
-            raise ValueError(f"lc_amd.gtinfo: scene_index is needed to tell which of the {S} scenes each of the {B} instances belongs to")
-    else:
-        _i32("scene_index", scene_index, (B,))
-    return Dt, S
-
-
-def _scene_index(scene_index, S: int, B: int, dev) -> Tensor:
-    if scene_index is None:
-        return torch.zeros(B, device=dev, dtype=torch.int32) if S == 1 else torch.arange(B, device=dev, dtype=torch.int32)
-    return scene_index.to(torch.int32).contiguous()
 
 
 def _window(h: int, w: int, H: int, W: int, origin_xy, B: int, placed: bool = False):
@@ -184,13 +104,9 @@ def _window(h: int, w: int, H: int, W: int, origin_xy, B: int, placed: bool = Fa
     if h * w >= 2 ** 31:
         raise ValueError(f"lc_amd.gtinfo: a window of {h} x {w} pixels overflows the int32 counts")
     if origin_xy is not None:
-        _i32("origin_xy", origin_xy, (B, 2))
+        _A.i32("origin_xy", origin_xy, (B, 2))
     elif not placed and (h, w) != (H, W):
         raise ValueError(f"lc_amd.gtinfo: without origin_xy the maps ({h} x {w}) must have the frame's size ({H} x {W})")
-
-
-def _fail(lib, what: str, rc: int):
-    raise RuntimeError(f"lc_amd.{what} failed (code {rc}): {lib.lc_amd_gtinfo_last_error().decode(errors='replace')}")
 
 
 @torch.no_grad()
@@ -198,31 +114,29 @@ def gt_info_from_depth(depth_gt, depth_test, K, *, delta, scene_index=None, orig
     """depth_gt (B,h,w); depth_test (H,W) or (S,H,W) with scene_index (B,) int32 / int64 (default: the one scene, or scene b for instance b
     when S = B); K (3,3) or (B,3,3); origin_xy (B,2) int32 / int64 = (x0,y0) of the (h,w) maps in the (H,W) frame, anywhere, or None for
     full-frame maps."""
-    delta = _delta(delta)
-    pcx, pcy = _center(pixel_center)
-    Dg = _f32("depth_gt", depth_gt, (None, None, None))
+    delta = _A.delta(delta)
+    pcx, pcy = _A.center(pixel_center)
+    Dg = _A.f32("depth_gt", depth_gt, (None, None, None))
     B, h, w = (int(n) for n in Dg.shape)
-    Dt, S = _scenes(depth_test, scene_index, B)
+    Dt, S = _A.scenes(depth_test, scene_index, B, "instances")
     H, W = int(Dt.shape[1]), int(Dt.shape[2])
-    if isinstance(K, Tensor) and tuple(K.shape) == (3, 3):
-        K = K.expand(B, 3, 3)
-    Kc = _f32("K", K, (B, 3, 3))
+    Kc = _A.cam_K("K", K, B)
     _window(h, w, H, W, origin_xy, B)
     Dg = _lib.require_hip_f32("depth_gt", Dg)
     dev = Dg.device
-    _on(dev, "depth_gt", depth_test=Dt, K=Kc, scene_index=scene_index, origin_xy=origin_xy)
+    _A.same_device(dev, "depth_gt is on {}", depth_test=Dt, K=Kc, scene_index=scene_index, origin_xy=origin_xy)
     Dt, Kc = Dt.contiguous(), Kc.contiguous()
     org = None if origin_xy is None else origin_xy.to(torch.int32).contiguous()
     info = torch.empty(B, COLUMNS, device=dev, dtype=torch.int32)
     mask = torch.empty(B, h, w, device=dev, dtype=torch.bool) if want_mask else None
     if B:
-        idx = _scene_index(scene_index, S, B, dev)
+        idx = _A.scene_index(scene_index, S, B, dev)
         lib = load()
         with _lib.on_device(dev):
             rc = lib.lc_gtinfo_f32(_lib.ptr(Dg), _lib.ptr(org), _lib.ptr(Dt), _lib.ptr(idx), _lib.ptr(Kc), B, h, w, S, H, W, pcx, pcy, delta,
                                    _lib.ptr(info), _lib.ptr(mask), _lib.stream_ptr(dev))
         if rc != 0:
-            _fail(lib, "lc_gtinfo_f32", rc)
+            _SO.fail("lc_gtinfo_f32", rc)
     return GtInfo(info, mask)
 
 
@@ -236,13 +150,13 @@ def compose_scene_depth(depth_inst, scene_index, frame_hw, n_scenes, *, origin_x
         raise TypeError(f"lc_amd.gtinfo: n_scenes must be a whole number, got {type(n_scenes)}")
     if n_scenes < 1:
         raise ValueError(f"lc_amd.gtinfo: at least one scene, got n_scenes = {n_scenes}")
-    Di = _f32("depth_inst", depth_inst, (None, None, None))
+    Di = _A.f32("depth_inst", depth_inst, (None, None, None))
     B, h, w = (int(n) for n in Di.shape)
-    _i32("scene_index", scene_index, (B,))
+    _A.i32("scene_index", scene_index, (B,))
     _window(h, w, H, W, origin_xy, B)
     Di = _lib.require_hip_f32("depth_inst", Di)
     dev = Di.device
-    _on(dev, "depth_inst", scene_index=scene_index, origin_xy=origin_xy)
+    _A.same_device(dev, "depth_inst is on {}", scene_index=scene_index, origin_xy=origin_xy)
     idx = scene_index.to(torch.int32).contiguous()
     org = None if origin_xy is None else origin_xy.to(torch.int32).contiguous()
     depth = torch.empty(n_scenes, H, W, device=dev, dtype=torch.float32)
@@ -255,7 +169,7 @@ def compose_scene_depth(depth_inst, scene_index, frame_hw, n_scenes, *, origin_x
         rc = lib.lc_scene_compose_f32(_lib.ptr(Di) if B else None, _lib.ptr(org) if B else None, _lib.ptr(idx) if B else None, B, h, w, n_scenes, H, W,
                                       _lib.ptr(depth), _lib.ptr(inst), _lib.ptr(info) if B else None, _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
     if rc != 0:
-        _fail(lib, "lc_scene_compose_f32", rc)
+        _SO.fail("lc_scene_compose_f32", rc)
     return SceneDepth(depth, inst, info)
 
 
@@ -277,20 +191,9 @@ def compute_gt_info(meshes, mesh_index, R, t, K, depth_test, *, frame_hw=None, m
 
     if not isinstance(meshes, _render.MeshSet):
         raise TypeError(f"lc_amd.gtinfo: meshes must be a lc_amd.render.MeshSet, got {type(meshes)}")
-    delta = _delta(delta)
-    _center(pixel_center)
-    if not isinstance(mesh_index, Tensor) or mesh_index.dtype != torch.int32:
-        raise TypeError("lc_amd.gtinfo: mesh_index must be an int32 tensor on the GPU (MeshSet.index_of)")
-    if mesh_index.dim() != 1:
-        raise ValueError(f"lc_amd.gtinfo: mesh_index has shape {tuple(mesh_index.shape)}, expected (B,)")
-    B = int(mesh_index.shape[0])
-    Rc = _f32("R", R, (B, 3, 3))
-    if isinstance(t, Tensor) and tuple(t.shape) not in ((B, 3), (B, 3, 1)):
-        raise ValueError(f"lc_amd.gtinfo: t has shape {tuple(t.shape)}, expected {(B, 3)} or {(B, 3, 1)}")
-    tc = _f32("t", t.reshape(B, 3) if isinstance(t, Tensor) else t, (B, 3))
-    if isinstance(K, Tensor) and tuple(K.shape) == (3, 3):
-        K = K.expand(B, 3, 3)
-    Kc = _f32("K", K, (B, 3, 3))
+    delta = _A.delta(delta)
+    _A.center(pixel_center)
+    B, (Rc,), (tc,), Kc = _A.pose_batch(mesh_index, dict(R=R), dict(t=t), K)
     if depth_test is None:
         if frame_hw is None:
             raise ValueError("lc_amd.gtinfo: without depth_test the scene is composed from the renders, and frame_hw = (H, W) is needed")
@@ -301,12 +204,12 @@ def compute_gt_info(meshes, mesh_index, R, t, K, depth_test, *, frame_hw=None, m
                 raise ValueError(f"lc_amd.gtinfo: scene_index is needed to tell which of the {n_scenes} scenes each instance belongs to")
             S = 1
         else:
-            _i32("scene_index", scene_index, (B,))
+            _A.i32("scene_index", scene_index, (B,))
             if isinstance(n_scenes, bool) or not isinstance(n_scenes, int) or n_scenes < 1:
                 raise ValueError("lc_amd.gtinfo: with scene_index and no depth_test, n_scenes says how many scenes to compose")
             S = n_scenes
     else:
-        Dt, S = _scenes(depth_test, scene_index, B)
+        Dt, S = _A.scenes(depth_test, scene_index, B, "instances")
         H, W = int(Dt.shape[1]), int(Dt.shape[2])
         if frame_hw is not None and tuple(_size("frame_hw", frame_hw, MAX_FRAME)) != (H, W):
             raise ValueError(f"lc_amd.gtinfo: frame_hw = {tuple(frame_hw)} but depth_test is {H} x {W}")
@@ -319,16 +222,14 @@ def compute_gt_info(meshes, mesh_index, R, t, K, depth_test, *, frame_hw=None, m
     dev = meshes.device
     if window_xy is not None:
         h, w = _size("window_hw", window_hw, MAX_WINDOW)
-        _i32("window_xy", window_xy, (B, 2))
+        _A.i32("window_xy", window_xy, (B, 2))
     else:
-        mx, my = _pair("margin", (0, 0) if margin is None else margin)
+        mx, my = _A.pair("margin", (0, 0) if margin is None else margin)
         if isinstance(mx, bool) or isinstance(my, bool) or not isinstance(mx, int) or not isinstance(my, int) or mx < 0 or my < 0:
             raise ValueError(f"lc_amd.gtinfo: margin = (mx, my) holds two whole numbers that are not negative, got {margin!r}")
         h, w = H + 2 * my, W + 2 * mx
     _window(h, w, H, W, window_xy, B, placed=True)
-    for name, x in (("mesh_index", mesh_index), ("R", Rc), ("t", tc), ("K", Kc), ("depth_test", Dt), ("scene_index", scene_index), ("window_xy", window_xy)):
-        if x is not None and x.device != dev:
-            raise RuntimeError(f"lc_amd.gtinfo: {name} is on {x.device}, the meshes are on {dev} (there is no CPU fallback in the product path)")
+    _A.same_device(dev, _args.MESHES_ON, mesh_index=mesh_index, R=Rc, t=tc, K=Kc, depth_test=Dt, scene_index=scene_index, window_xy=window_xy)
     if window_xy is not None:
         origin = window_xy.to(torch.int32).contiguous()
     else:
@@ -338,7 +239,7 @@ def compute_gt_info(meshes, mesh_index, R, t, K, depth_test, *, frame_hw=None, m
     Kr[:, 1, 2] -= origin[:, 1].to(torch.float32)
     out = _render.render_depth(meshes, mesh_index, Rc, tc, Kr, (h, w), near=near, far=far, pixel_center=pixel_center)
     known = (mesh_index >= 0) & (mesh_index < meshes.n_meshes)
-    idx = torch.where(known, _scene_index(scene_index, S, B, dev), torch.full_like(mesh_index, -1))  # an unknown mesh: refused by the record as well
+    idx = torch.where(known, _A.scene_index(scene_index, S, B, dev), torch.full_like(mesh_index, -1))  # an unknown mesh: refused by the record as well
     scene = None
     if Dt is None:
         scene = compose_scene_depth(out.depth, idx, (H, W), S, origin_xy=origin, want_instance=True)

@@ -16,14 +16,13 @@ its outputs only and can be captured into a graph.  The loader's retry on `valid
 """
 from __future__ import annotations
 
-import ctypes
 from ctypes import c_int, c_size_t, c_uint64, c_void_p
 from typing import NamedTuple, Optional
 
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
 from . import build as _build
 
 MAX_SIZE = 16384           # LC_MASKCROP_MAX_SIZE
@@ -43,42 +42,12 @@ class MaskCrops(NamedTuple):
     info: Tensor                    # (B,) int32: 0, -1 for a refused row
 
 
-_LIB = None
-_SIGNATURES = {
-    "lc_amd_maskcrop_version": (c_int, []),
-    "lc_amd_maskcrop_last_error": (ctypes.c_char_p, []),
-    "lc_amd_maskcrop_source_hash": (ctypes.c_char_p, []),
+_SO = _lib.SideLibrary(_build.MASKCROP, {
     "lc_mask_crops_workspace_bytes": (c_size_t, [c_int] * 6),
     "lc_mask_crops_u8": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 3 + [c_int] * 6 + [c_uint64, c_void_p, c_int] + [c_void_p] * 6 + [c_size_t, c_void_p]),
-}
-
-
-def load(build_if_missing: bool = True):
-    """liblc_amd_maskcrop.so, loaded on first use by `_lib.load_target`: a library built from other sources than the ones next to it is
-    rebuilt, or refused where hipcc is absent (unless LC_AMD_ALLOW_STALE=1)."""
-    global _LIB
-    if _LIB is None:
-        _LIB = _lib.load_target(_build.MASKCROP, _SIGNATURES, build_if_missing)
-    return _LIB
-
-
-def _tensor(name, t, dtypes, what, shape):
-    """Type, element type and shape (None: any size)."""
-    if not isinstance(t, Tensor):
-        raise TypeError(f"lc_amd.maskcrop: {name} must be a torch.Tensor, got {type(t)}")
-    if t.dtype not in dtypes:
-        raise TypeError(f"lc_amd.maskcrop: {name} must be {what}, got {t.dtype}")
-    if t.dim() != len(shape) or any(want is not None and have != want for have, want in zip(t.shape, shape)):
-        raise ValueError(f"lc_amd.maskcrop: {name} has shape {tuple(t.shape)}, expected ({', '.join('*' if d is None else str(d) for d in shape)})")
-    return t
-
-
-def _whole(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, int):
-        raise TypeError(f"lc_amd.maskcrop: {name} must be a whole number, got {type(v)}")
-    if not (lo <= v <= hi):
-        raise ValueError(f"lc_amd.maskcrop: {name} of {lo} to {hi}, got {v}")
-    return v
+})
+_SIGNATURES, load = _SO.signatures, _SO.load
+_A = _args.Args("maskcrop")  # its whole numbers are Python's own (`whole` without numpy=True)
 
 
 @torch.no_grad()
@@ -101,20 +70,18 @@ def mask_crops(masks, M, out_hw, *, mask_index=None, origin=None, vis_interp="li
 
     Called with the in-matrix at the network's INPUT size, n_check=0 and want=("msk_vis",), it yields `msk_in`, the mask the reference's
     background switch blends with (`dataset.py:414`)."""
-    masks = _tensor("masks", masks, (torch.uint8, torch.bool), "uint8 or bool", (None, None, None))
-    M = _tensor("M", M, (torch.float32,), "float32", (None, 2, 3))
-    if isinstance(out_hw, (Tensor, str)) or not hasattr(out_hw, "__len__") or len(out_hw) != 2:
-        raise ValueError(f"lc_amd.maskcrop: out_hw is a pair, got {out_hw!r}")
-    h, w = _whole("out_hw", out_hw[0], 1, MAX_SIZE), _whole("out_hw", out_hw[1], 1, MAX_SIZE)
+    masks = _A.tensor("masks", masks, (torch.uint8, torch.bool), "uint8 or bool", (None, None, None))
+    M = _A.tensor("M", M, (torch.float32,), "float32", (None, 2, 3))
+    h, w = _A.size_pair("out_hw", out_hw, MAX_SIZE)
     F, Hm, Wm = (int(s) for s in masks.shape)
     B = int(M.shape[0])
     if not (1 <= Hm <= MAX_SIZE and 1 <= Wm <= MAX_SIZE):
         raise ValueError(f"lc_amd.maskcrop: mask sizes of 1 to {MAX_SIZE}, got {Hm} x {Wm}")
     if vis_interp not in INTERP:
         raise ValueError(f"lc_amd.maskcrop: vis_interp must be one of {sorted(INTERP)}, got {vis_interp!r}")
-    valid_th = _whole("valid_th", valid_th, -2 ** 31, 2 ** 31 - 1)
-    n_check = _whole("n_check", n_check, 0, MAX_CHECK)
-    seed = _whole("seed", seed, 0, 2 ** 64 - 1)
+    valid_th = _A.whole("valid_th", valid_th, -2 ** 31, 2 ** 31 - 1)
+    n_check = _A.whole("n_check", n_check, 0, MAX_CHECK)
+    seed = _A.whole("seed", seed, 0, 2 ** 64 - 1)
     if ck_dtype not in CK_DTYPES:
         raise TypeError(f"lc_amd.maskcrop: ck_dtype must be torch.int32 or torch.int64, got {ck_dtype}")
     if isinstance(want, str) or any(name not in OUTPUTS for name in want):
@@ -129,23 +96,21 @@ def mask_crops(masks, M, out_hw, *, mask_index=None, origin=None, vis_interp="li
     if checks and h * w > MAX_CHECK_PIXELS:
         raise ValueError(f"lc_amd.maskcrop: check points need a crop of at most {MAX_CHECK_PIXELS} pixels, got {h} x {w}")
     if mask_index is not None:
-        _tensor("mask_index", mask_index, (torch.int32,), "int32", (B,))
+        _A.tensor("mask_index", mask_index, (torch.int32,), "int32", (B,))
     if origin is not None:
-        _tensor("origin", origin, (torch.int32, torch.int64), "int32 or int64", (B, 2))
+        _A.tensor("origin", origin, (torch.int32, torch.int64), "int32 or int64", (B, 2))
     if sample_id is not None:
-        _tensor("sample_id", sample_id, (torch.int32,), "int32", (B,))
+        _A.tensor("sample_id", sample_id, (torch.int32,), "int32", (B,))
     shapes = dict(msk_vis=((torch.float32,), "float32", (B, h, w)), msk_noc=((torch.bool, torch.uint8), "bool or uint8", (B, h, w)),
                   valid_cnt=((torch.int32,), "int32", (B,)), sym_ck_pts2d=((ck_dtype,), str(ck_dtype), (B, n_check, 2)), info=((torch.int32,), "int32", (B,)))
     for name, t in out.items():
-        _tensor(f"out[{name!r}]", t, *shapes[name])
+        _A.tensor(f"out[{name!r}]", t, *shapes[name])
         if not t.is_contiguous():
             raise ValueError(f"lc_amd.maskcrop: out[{name!r}] must be contiguous, got strides {tuple(t.stride())}")
     if not masks.is_cuda:
         raise RuntimeError(f"lc_amd.maskcrop: masks is on {masks.device}; the HIP path needs tensors on the MI355X (there is no CPU fallback in the product path)")
     dev = masks.device
-    for name, t in (("M", M), ("mask_index", mask_index), ("origin", origin), ("sample_id", sample_id), *((f"out[{k!r}]", v) for k, v in out.items())):
-        if t is not None and t.device != dev:
-            raise RuntimeError(f"lc_amd.maskcrop: {name} is on {t.device}, the masks on {dev}")
+    _A.same_device(dev, "the masks on {}", M=M, mask_index=mask_index, origin=origin, sample_id=sample_id, **{f"out[{k!r}]": v for k, v in out.items()})
     masks = masks.contiguous()
     m8 = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
     M = M.contiguous()
@@ -175,7 +140,7 @@ def mask_crops(masks, M, out_hw, *, mask_index=None, origin=None, vis_interp="li
                                       n_check if checks else 0, seed, _lib.ptr(sid), CK_DTYPES[ck_dtype], _lib.ptr(vis), _lib.ptr(noc), _lib.ptr(cnt),
                                       _lib.ptr(ck) if checks else None, _lib.ptr(info), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
         if rc != 0:
-            raise RuntimeError(f"lc_amd.maskcrop.mask_crops failed (code {rc}): {lib.lc_amd_maskcrop_last_error().decode(errors='replace')}")
+            _SO.fail("maskcrop.mask_crops", rc)
     if noc is not None and noc.dtype != torch.bool:
         noc = noc.view(torch.bool)
     return MaskCrops(vis, noc, cnt, ck, info)

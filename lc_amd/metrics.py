@@ -9,7 +9,7 @@ from ctypes import c_int, c_void_p
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
 from . import build as _build
 from .symmetry import SymmetrySet
 from .transforms import quaternion_rep_to_RT
@@ -45,23 +45,13 @@ def pose_errors_from_states(states_est: Tensor, states_gt: Tensor, pts: Tensor, 
     return compute_pose_errors(Re, te, Rg, tg, pts, **kw)
 
 
-_SYMERR_LIB = None
-_SYMERR_SIGNATURES = {
-    "lc_amd_symerr_version": (c_int, []),
-    "lc_amd_symerr_last_error": (ctypes.c_char_p, []),
-    "lc_amd_symerr_source_hash": (ctypes.c_char_p, []),
+_SYMERR = _lib.SideLibrary(_build.SYMERR, {
     "lc_sym_pose_errors_workspace_bytes": (ctypes.c_size_t, [c_int, c_int]),
     "lc_sym_pose_errors_f32": (c_int, [c_void_p] * 8 + [c_int] + [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 3 + [ctypes.c_size_t, c_void_p]),
-}
-
-
-def load_symerr(build_if_missing: bool = True):
-    """liblc_amd_symerr.so (C ABI in include/lc_amd_symerr.h), loaded on first use by `_lib.load_target`: a library built from other sources
-    than the ones next to it is rebuilt, or refused where hipcc is absent (unless LC_AMD_ALLOW_STALE=1)."""
-    global _SYMERR_LIB
-    if _SYMERR_LIB is None:
-        _SYMERR_LIB = _lib.load_target(_build.SYMERR, _SYMERR_SIGNATURES, build_if_missing)
-    return _SYMERR_LIB
+})
+_SYMERR_SIGNATURES, load_symerr = _SYMERR.signatures, _SYMERR.load  # liblc_amd_symerr.so (C ABI in include/lc_amd_symerr.h)
+_A = _args.Args("metrics")
+_POSES_ON = "the poses are on {}"
 
 
 _SYM_WS = {}  # (device index, bytes rounded up to a power of two) -> workspace; never freed: a captured graph may hold its address
@@ -79,27 +69,16 @@ def _sym_workspace(dev, nbytes: int) -> Tensor:
 
 
 def _hip_i32(name: str, t, B: int, dev) -> Tensor:
-    if not isinstance(t, Tensor):
-        raise TypeError(f"lc_amd.metrics: {name} must be a torch.Tensor, got {type(t)}")
-    if t.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"lc_amd.metrics: {name} must be int32 or int64, got {t.dtype}")
-    if tuple(t.shape) != (B,):
-        raise ValueError(f"lc_amd.metrics: {name} has shape {tuple(t.shape)}, expected {(B,)}")
-    if t.device != dev:
-        raise RuntimeError(f"lc_amd.metrics: {name} is on {t.device}, the poses are on {dev}")
+    _A.same_device(dev, _POSES_ON, **{name: _A.i32(name, t, (B,))})
     return t.to(torch.int32).contiguous()
 
 
 def _f32(name: str, t, shape, dev=None) -> Tensor:
-    """Type, element type, shape (None: any size) and the device of the poses; _lib.require_hip_f32 follows once every tensor has passed."""
-    if not isinstance(t, Tensor):
-        raise TypeError(f"lc_amd.metrics: {name} must be a torch.Tensor, got {type(t)}")
-    if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-        raise TypeError(f"lc_amd.metrics: {name} must be float32 (reference I/O precision), got {t.dtype}")
-    if t.dim() != len(shape) or any(want is not None and have != want for have, want in zip(t.shape, shape)):
-        raise ValueError(f"lc_amd.metrics: {name} has shape {tuple(t.shape)}, expected ({', '.join('*' if d is None else str(d) for d in shape)})")
-    if dev is not None and t.device != dev:
-        raise RuntimeError(f"lc_amd.metrics: {name} is on {t.device}, the poses are on {dev}")
+    """Type, element type (the 16-bit floats pass: _lib.require_hip_f32 up-casts them once every tensor has passed), shape (None: any
+    size) and the device of the poses."""
+    _A.tensor(name, t, (torch.float32, torch.float16, torch.bfloat16), "float32 (reference I/O precision)", shape)
+    if dev is not None:
+        _A.same_device(dev, _POSES_ON, **{name: t})
     return t
 
 
@@ -118,17 +97,9 @@ def compute_sym_pose_errors(R_est: Tensor, t_est: Tensor, R_gt: Tensor, t_gt: Te
         raise TypeError(f"lc_amd.metrics: syms must be a lc_amd.symmetry.SymmetrySet, got {type(syms)}")
     if isinstance(R_est, Tensor) and syms.device != R_est.device:
         raise RuntimeError(f"lc_amd.metrics: the SymmetrySet is on {syms.device}, the poses are on {R_est.device}")
-    Re = _f32("R_est", R_est, (None, 3, 3))
-    dev, B = Re.device, int(Re.shape[0])
-    Rg = _f32("R_gt", R_gt, (B, 3, 3), dev)
-    for name, t in (("t_est", t_est), ("t_gt", t_gt)):
-        if isinstance(t, Tensor) and tuple(t.shape) not in ((B, 3), (B, 3, 1)):
-            raise ValueError(f"lc_amd.metrics: {name} has shape {tuple(t.shape)}, expected {(B, 3)} or {(B, 3, 1)}")
-    te = _f32("t_est", t_est.reshape(B, 3) if isinstance(t_est, Tensor) else t_est, (B, 3), dev)
-    tg = _f32("t_gt", t_gt.reshape(B, 3) if isinstance(t_gt, Tensor) else t_gt, (B, 3), dev)
-    if isinstance(cam_K, Tensor) and tuple(cam_K.shape) == (3, 3):
-        cam_K = cam_K.expand(B, 3, 3)  # a view; made contiguous on the device below: nothing is read back
-    Kc = _f32("cam_K", cam_K, (B, 3, 3), dev)
+    dev = R_est.device if isinstance(R_est, Tensor) else None  # (anything else is refused by the first rule below)
+    B, (Re, Rg), (te, tg), Kc = _A.pose_batch(None, dict(R_est=R_est, R_gt=R_gt), dict(t_est=t_est, t_gt=t_gt), cam_K, "cam_K",
+                                              lambda name, t, shape: _f32(name, t, shape, dev))
     Re, Rg, te, tg, Kc = (_lib.require_hip_f32(n, t) for n, t in (("R_est", Re), ("R_gt", Rg), ("t_est", te), ("t_gt", tg), ("cam_K", Kc)))
     lib = load_symerr()
     idx = _hip_i32("obj_index", obj_index, B, dev)
@@ -169,7 +140,7 @@ def compute_sym_pose_errors(R_est: Tensor, t_est: Tensor, R_gt: Tensor, t_gt: Te
                                             _lib.ptr(syms.obj_k), syms.n_obj, syms.total, syms.max_k, B, _lib.ptr(err), _lib.ptr(arg), _lib.ptr(ws),
                                             ws.numel() * 8, _lib.stream_ptr(dev))
         if rc != 0:
-            raise RuntimeError(f"lc_amd.lc_sym_pose_errors_f32 failed (code {rc}): {lib.lc_amd_symerr_last_error().decode(errors='replace')}")
+            _SYMERR.fail("lc_sym_pose_errors_f32", rc)
     return dict(mssd=err[:, 0], mspd=err[:, 1], proj=err[:, 2], mssd_sym=arg[:, 0], mspd_sym=arg[:, 1])
 
 

@@ -30,24 +30,12 @@ from .render import MeshSet  # (importing it does not load the render library)
 DIAM_TILE = 256        # LC_MODEL_DIAM_TILE: vertices along the edge of one tile of the pair matrix
 FPS_RESIDENT = 8192    # LC_MODEL_FPS_RESIDENT: up to here a mesh's coordinates and distances stay in registers during the selection
 
-_LIB = None
-_SIGNATURES = {
-    "lc_amd_models_version": (c_int, []),
-    "lc_amd_models_last_error": (ctypes.c_char_p, []),
-    "lc_amd_models_source_hash": (ctypes.c_char_p, []),
+_SO = _lib.SideLibrary(_build.MODELS, {
     "lc_model_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     # the mesh table is passed twice: on the device, and as a HOST int array the argument rules are checked from
     "lc_model_prepare_f32": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_int), c_int, c_int, c_int] + [c_void_p] * 7 + [c_size_t, c_void_p]),
-}
-
-
-def load(build_if_missing: bool = True):
-    """liblc_amd_models.so, loaded on first use by `_lib.load_target`: a library built from other sources than the ones next to it is
-    rebuilt, or refused where hipcc is absent (unless LC_AMD_ALLOW_STALE=1)."""
-    global _LIB
-    if _LIB is None:
-        _LIB = _lib.load_target(_build.MODELS, _SIGNATURES, build_if_missing)
-    return _LIB
+})
+_SIGNATURES, load = _SO.signatures, _SO.load
 
 
 class ModelInfo(NamedTuple):
@@ -99,7 +87,7 @@ def prepare(meshes: MeshSet, fps_count: int = 0, *, want_diameter: bool = True, 
                                       max_verts, fps_count, _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(diameter), _lib.ptr(pair), _lib.ptr(fps),
                                       _lib.ptr(fps_index), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
     if rc != 0:
-        raise RuntimeError(f"lc_amd.models.prepare failed (code {rc}): {lib.lc_amd_models_last_error().decode(errors='replace')}")
+        _SO.fail("models.prepare", rc)
     return ModelInfo(lo, hi, diameter, pair, fps, fps_index)
 
 

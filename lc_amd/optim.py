@@ -16,7 +16,6 @@ puts this class in place of the reference's.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from ctypes import c_int, c_void_p
 
@@ -39,22 +38,8 @@ TENSOR = np.dtype([("p", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"), ("sl
 BLOCK = np.dtype([("tensor", "<i4"), ("n", "<i4"), ("e0", "<i8")])
 assert SCALARS.itemsize == 48 and TENSOR.itemsize == 56 and BLOCK.itemsize == 16
 
-_LIB = None
-_SIGNATURES = {
-    "lc_amd_optim_version": (c_int, []),
-    "lc_amd_optim_last_error": (ctypes.c_char_p, []),
-    "lc_amd_optim_source_hash": (ctypes.c_char_p, []),
-    "lc_ranger_step_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-}
-
-
-def load(build_if_missing: bool = True):
-    """liblc_amd_optim.so, loaded on first use by `_lib.load_target`: a library built from other sources than the ones next to it is
-    rebuilt, or refused where hipcc is absent (unless LC_AMD_ALLOW_STALE=1)."""
-    global _LIB
-    if _LIB is None:
-        _LIB = _lib.load_target(_build.OPTIM, _SIGNATURES, build_if_missing)
-    return _LIB
+_SO = _lib.SideLibrary(_build.OPTIM, {"lc_ranger_step_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p])})
+_SIGNATURES, load = _SO.signatures, _SO.load
 
 
 def _dense(t: torch.Tensor) -> bool:
@@ -251,7 +236,7 @@ class Ranger(Optimizer):
             rc = lib.lc_ranger_step_f32(c_void_p(self._table.data_ptr()), self._ntensors, self._nrowsum, self._nupdate,
                                         c_void_p(self._means.data_ptr()), _lib.stream_ptr(self._device))
             if rc != 0:
-                raise RuntimeError(f"lc_amd.optim.Ranger.step failed (code {rc}): {lib.lc_amd_optim_last_error().decode(errors='replace')}")
+                _SO.fail("optim.Ranger.step", rc)
             for g, tmp in staged:
                 g.copy_(tmp)
         return None

@@ -20,14 +20,13 @@ can be captured into a graph.
 """
 from __future__ import annotations
 
-import ctypes
 from ctypes import c_int, c_void_p
 from typing import NamedTuple
 
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
 from . import build as _build
 
 NAN_TO_NUM, WEIGHTS_ARE_STD, SCALAR_WEIGHTS, COV_2D = 1, 2, 4, 8  # include/lc_amd_posecov.h: LC_POSE_COV_*
@@ -41,27 +40,9 @@ class PoseCov(NamedTuple):
     info: Tensor      # (B,) int32: 0 = the Hessian was positive definite
 
 
-_LIB = None
-_SIGNATURES = {
-    "lc_amd_posecov_version": (c_int, []),
-    "lc_amd_posecov_last_error": (ctypes.c_char_p, []),
-    "lc_amd_posecov_source_hash": (ctypes.c_char_p, []),
-    "lc_pose_cov_f32": (c_int, [c_void_p] * 8 + [c_int] * 5 + [c_void_p] * 5),
-}
-
-
-def load(build_if_missing: bool = True):
-    """liblc_amd_posecov.so, loaded on first use by `_lib.load_target`: a library built from other sources than the ones next to it is
-    rebuilt, or refused where hipcc is absent (unless LC_AMD_ALLOW_STALE=1)."""
-    global _LIB
-    if _LIB is None:
-        _LIB = _lib.load_target(_build.POSECOV, _SIGNATURES, build_if_missing)
-    return _LIB
-
-
-def _shape(name, t, shape):
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"lc_amd.posecov: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+_SO = _lib.SideLibrary(_build.POSECOV, {"lc_pose_cov_f32": (c_int, [c_void_p] * 8 + [c_int] * 5 + [c_void_p] * 5)})
+_SIGNATURES, load = _SO.signatures, _SO.load
+_A = _args.Args("posecov")
 
 
 @torch.no_grad()
@@ -80,30 +61,28 @@ def pose_covariance(K, pts3d, pts2d, weights, pose, counts=None, *, bbox_3d, dia
     if not 1 <= N <= MAX_POINTS:
         raise ValueError(f"lc_amd.posecov: rows of 1 to {MAX_POINTS} points, got N = {N}")
     dev = X.device
-    _shape("pts2d", U, (B, N, 2))
+    _A.rows("pts2d", U, (B, N, 2))
     if Wt.dim() == 2:
-        _shape("weights", Wt, (B, N))
+        _A.rows("weights", Wt, (B, N))
     else:
-        _shape("weights", Wt, (B, N, 2))
+        _A.rows("weights", Wt, (B, N, 2))
     P = int(shared_poses) if shared_poses else B
     if P < 1 or B % P:
         raise ValueError(f"lc_amd.posecov: shared_poses = {shared_poses} does not divide the batch of {B} rows")
-    _shape("K", K, (P, 3, 3))
-    _shape("bbox_3d", bbox, (P, 8, 3))
+    _A.rows("K", K, (P, 3, 3))
+    _A.rows("bbox_3d", bbox, (P, 8, 3))
     if pose.dim() != 2 or pose.shape[1] != 7 or pose.shape[0] not in (P, B):
         raise ValueError(f"lc_amd.posecov: pose must be ({P},7)" + (f" or ({B},7)" if P != B else "") + f", got {tuple(pose.shape)}")
     if diam is not None:
         if cov_2d:
             raise ValueError("lc_amd.posecov: diameter divides the 3D corner error only (loss_cov_2d takes none)")
-        _shape("diameter", diam, (P,))
+        _A.rows("diameter", diam, (P,))
     if counts is not None:
         if not isinstance(counts, Tensor) or not counts.is_cuda or counts.dtype != torch.int32:
             raise TypeError("lc_amd.posecov: counts must be an int32 tensor on the GPU")
-        _shape("counts", counts, (B,))
+        _A.rows("counts", counts, (B,))
         counts = counts.contiguous()
-    for name, t in (("K", K), ("pts2d", U), ("weights", Wt), ("pose", pose), ("bbox_3d", bbox), ("diameter", diam), ("counts", counts)):
-        if t is not None and t.device != dev:
-            raise RuntimeError(f"lc_amd.posecov: {name} is on {t.device}, pts3d on {dev}")
+    _A.same_device(dev, "pts3d on {}", K=K, pts2d=U, weights=Wt, pose=pose, bbox_3d=bbox, diameter=diam, counts=counts)
     lib = load()
     rows = 16 if cov_2d else 24
     cov = torch.empty(B, 6, 6, device=dev, dtype=torch.float32)
@@ -115,5 +94,5 @@ def pose_covariance(K, pts3d, pts2d, weights, pose, counts=None, *, bbox_3d, dia
         rc = lib.lc_pose_cov_f32(_lib.ptr(K), _lib.ptr(pose), _lib.ptr(X), _lib.ptr(U), _lib.ptr(Wt), _lib.ptr(counts), _lib.ptr(bbox), _lib.ptr(diam),
                                  B, N, opts, P, int(pose.shape[0]), _lib.ptr(cov), _lib.ptr(var), _lib.ptr(perr), _lib.ptr(info), _lib.stream_ptr(dev))
     if rc != 0:
-        raise RuntimeError(f"lc_amd.posecov.pose_covariance failed (code {rc}): {lib.lc_amd_posecov_last_error().decode(errors='replace')}")
+        _SO.fail("posecov.pose_covariance", rc)
     return PoseCov(cov, var, perr, info)

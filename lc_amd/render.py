@@ -22,7 +22,6 @@ can be captured into a graph.
 """
 from __future__ import annotations
 
-import ctypes
 from ctypes import c_float, c_int, c_size_t, c_void_p
 from typing import NamedTuple, Optional
 
@@ -30,7 +29,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
 from . import build as _build
 
 MAX_SIZE = 16384   # LC_RENDER_MAX_SIZE
@@ -45,23 +44,12 @@ class Rendered(NamedTuple):
     info: Tensor              # (B,) int32: faces dropped at the near plane; -1 = mesh_index outside the set
 
 
-_LIB = None
-_SIGNATURES = {
-    "lc_amd_render_version": (c_int, []),
-    "lc_amd_render_last_error": (ctypes.c_char_p, []),
-    "lc_amd_render_source_hash": (ctypes.c_char_p, []),
+_SO = _lib.SideLibrary(_build.RENDER, {
     "lc_render_workspace_bytes": (c_size_t, [c_int, c_int]),
     "lc_render_depth_f32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 4 + [c_int] * 3 + [c_float] * 4 + [c_void_p] * 6 + [c_size_t, c_void_p]),
-}
-
-
-def load(build_if_missing: bool = True):
-    """liblc_amd_render.so, loaded on first use by `_lib.load_target`: a library built from other sources than the ones next to it is
-    rebuilt, or refused where hipcc is absent (unless LC_AMD_ALLOW_STALE=1)."""
-    global _LIB
-    if _LIB is None:
-        _LIB = _lib.load_target(_build.RENDER, _SIGNATURES, build_if_missing)
-    return _LIB
+})
+_SIGNATURES, load = _SO.signatures, _SO.load
+_A = _args.Args("render")
 
 
 class MeshSet:
@@ -123,11 +111,6 @@ class MeshSet:
         return self._lut[ids]
 
 
-def _rows(name, t, shape):
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"lc_amd.render: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
-
-
 @torch.no_grad()
 def render_depth(meshes: MeshSet, mesh_index, R, t, K, size_hw, *, near, far, pixel_center=(0.5, 0.5), want_face=False, want_homo=False,
                  pix2k=None) -> Rendered:
@@ -141,20 +124,18 @@ def render_depth(meshes: MeshSet, mesh_index, R, t, K, size_hw, *, near, far, pi
         raise TypeError("lc_amd.render: mesh_index must be an int32 tensor on the GPU (MeshSet.index_of)")
     B = int(mesh_index.shape[0])
     H, W = int(size_hw[0]), int(size_hw[1])
-    _rows("mesh_index", mesh_index, (B,))
+    _A.rows("mesh_index", mesh_index, (B,))
     R, t = R.reshape(-1, 3, 3), t.reshape(-1, 3)
-    _rows("R", R, (B, 3, 3))
-    _rows("t", t, (B, 3))
-    _rows("K", K, (B, 3, 3))
+    _A.rows("R", R, (B, 3, 3))
+    _A.rows("t", t, (B, 3))
+    _A.rows("K", K, (B, 3, 3))
     if M is not None:
-        _rows("pix2k", M, (B, 2, 3))
+        _A.rows("pix2k", M, (B, 2, 3))
         want_homo = True
     if not (1 <= H <= MAX_SIZE and 1 <= W <= MAX_SIZE):
         raise ValueError(f"lc_amd.render: map sizes of 1 to {MAX_SIZE}, got {H} x {W}")
     dev = meshes.device
-    for name, x in (("mesh_index", mesh_index), ("R", R), ("t", t), ("K", K), ("pix2k", M)):
-        if x is not None and x.device != dev:
-            raise RuntimeError(f"lc_amd.render: {name} is on {x.device}, the meshes on {dev}")
+    _A.same_device(dev, "the meshes on {}", mesh_index=mesh_index, R=R, t=t, K=K, pix2k=M)
     mesh_index = mesh_index.contiguous()
     lib = load()
     depth = torch.empty(B, H, W, device=dev, dtype=torch.float32)
@@ -170,7 +151,7 @@ def render_depth(meshes: MeshSet, mesh_index, R, t, K, size_hw, *, near, far, pi
                                      B, H, W, float(near), float(far), float(pixel_center[0]), float(pixel_center[1]), _lib.ptr(depth),
                                      _lib.ptr(face), _lib.ptr(mask), _lib.ptr(homo), _lib.ptr(info), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
     if rc != 0:
-        raise RuntimeError(f"lc_amd.render.render_depth failed (code {rc}): {lib.lc_amd_render_last_error().decode(errors='replace')}")
+        _SO.fail("render.render_depth", rc)
     return Rendered(depth, mask, face, homo, info)
 
 

@@ -24,7 +24,6 @@ never wait for the device, allocate their outputs only (none with `out=`) and ca
 """
 from __future__ import annotations
 
-import ctypes
 from ctypes import c_int, c_int64, c_void_p
 from typing import NamedTuple, Optional
 
@@ -32,7 +31,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
 from . import build as _build
 
 MAX_SIZE = 16384           # LC_RLE_MAX_SIZE
@@ -47,28 +46,13 @@ class Encoded(NamedTuple):
     info: Tensor     # (F,) int32: 0, -2 where cap was too small (the row is zero, n_runs the needed number), -1 for a bad size or origin
 
 
-_LIB = None
-_SIGNATURES = {
-    "lc_amd_rle_version": (c_int, []),
-    "lc_amd_rle_last_error": (ctypes.c_char_p, []),
-    "lc_amd_rle_source_hash": (ctypes.c_char_p, []),
+_SO = _lib.SideLibrary(_build.RLE, {
     "lc_rle_index_u32": (c_int, [c_void_p] * 3 + [c_int64, c_int] + [c_void_p] * 5),
     "lc_rle_decode_u8": (c_int, [c_void_p] * 4 + [c_int64, c_int] + [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 3),
     "lc_rle_encode_u8": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 2 + [c_int] + [c_void_p] * 4),
-}
-
-
-def load(build_if_missing: bool = True):
-    """liblc_amd_rle.so, loaded on first use by `_lib.load_target`: a library built from other sources than the ones next to it is
-    rebuilt, or refused where hipcc is absent (unless LC_AMD_ALLOW_STALE=1)."""
-    global _LIB
-    if _LIB is None:
-        _LIB = _lib.load_target(_build.RLE, _SIGNATURES, build_if_missing)
-    return _LIB
-
-
-def _fail(lib, what, rc):
-    raise RuntimeError(f"lc_amd.rle.{what} failed (code {rc}): {lib.lc_amd_rle_last_error().decode(errors='replace')}")
+})
+_SIGNATURES, load = _SO.signatures, _SO.load
+_A = _args.Args("rle")  # its whole numbers may be numpy's (`numpy=True`)
 
 
 # ---- COCO's compressed string, on the host
@@ -126,28 +110,8 @@ def string_to_counts(s) -> np.ndarray:
 # ---- argument rules
 
 
-def _tensor(name, t, dtypes, what, shape):
-    if not isinstance(t, Tensor):
-        raise TypeError(f"lc_amd.rle: {name} must be a torch.Tensor, got {type(t)}")
-    if t.dtype not in dtypes:
-        raise TypeError(f"lc_amd.rle: {name} must be {what}, got {t.dtype}")
-    if t.dim() != len(shape) or any(want is not None and have != want for have, want in zip(t.shape, shape)):
-        raise ValueError(f"lc_amd.rle: {name} has shape {tuple(t.shape)}, expected ({', '.join('*' if d is None else str(d) for d in shape)})")
-    return t
-
-
-def _whole(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise TypeError(f"lc_amd.rle: {name} must be a whole number, got {type(v)}")
-    if not (lo <= int(v) <= hi):
-        raise ValueError(f"lc_amd.rle: {name} of {lo} to {hi}, got {int(v)}")
-    return int(v)
-
-
 def _pair(name, hw):
-    if isinstance(hw, (Tensor, str)) or not hasattr(hw, "__len__") or len(hw) != 2:
-        raise ValueError(f"lc_amd.rle: {name} is a pair, got {hw!r}")
-    return _whole(name, hw[0], 1, MAX_SIZE), _whole(name, hw[1], 1, MAX_SIZE)
+    return _A.size_pair(name, hw, MAX_SIZE, numpy=True)
 
 
 def _device(device):
@@ -176,17 +140,15 @@ class RleStore:
     (F,) int32, 0 or -1.  The arrays are device data: the kernels judge them, and whoever overwrites them in place calls `index()` again."""
 
     def __init__(self, counts, offsets, sizes, frame_hw=None):
-        _tensor("counts", counts, (torch.int32,), "int32 (holding uint32 bits)", (None,))
-        _tensor("offsets", offsets, (torch.int64,), "int64", (None,))
+        _A.tensor("counts", counts, (torch.int32,), "int32 (holding uint32 bits)", (None,))
+        _A.tensor("offsets", offsets, (torch.int64,), "int64", (None,))
         if offsets.shape[0] < 1:
             raise ValueError("lc_amd.rle: offsets holds F + 1 entries, got none")
         F = int(offsets.shape[0]) - 1
-        _tensor("sizes", sizes, (torch.int32,), "int32", (F, 2))
+        _A.tensor("sizes", sizes, (torch.int32,), "int32", (F, 2))
         if not counts.is_cuda:
             raise RuntimeError(f"lc_amd.rle: counts is on {counts.device}; the HIP path needs tensors on the MI355X (there is no CPU fallback in the product path)")
-        for name, t in (("offsets", offsets), ("sizes", sizes)):
-            if t.device != counts.device:
-                raise RuntimeError(f"lc_amd.rle: {name} is on {t.device}, the counts on {counts.device}")
+        _A.same_device(counts.device, "the counts on {}", offsets=offsets, sizes=sizes)
         if counts.shape[0] > MAX_COUNTS:
             raise ValueError(f"lc_amd.rle: at most {MAX_COUNTS} counts, got {counts.shape[0]}")
         self.counts, self.offsets, self.sizes = counts.contiguous(), offsets.contiguous(), sizes.contiguous()
@@ -210,7 +172,7 @@ class RleStore:
                 rc = lib.lc_rle_index_u32(_lib.ptr(self.counts), _lib.ptr(self.offsets), _lib.ptr(self.sizes), self.T, self.F, _lib.ptr(self.ends), _lib.ptr(self.area),
                                           _lib.ptr(self.box), _lib.ptr(self.valid), _lib.stream_ptr(self.device))
             if rc != 0:
-                _fail(lib, "RleStore.index", rc)
+                _SO.fail("rle.RleStore.index", rc)
         return self
 
     @classmethod
@@ -292,7 +254,7 @@ class RleStore:
         """(B,2) int32 (x0, y0) of (Hm, Wm) windows centred on the boxes of masks `index` ((B,) int32 / int64, or None for all): the box
         centre (x_min + x_max + 1) / 2 less half the window, floored; (0, 0) for an empty mask.  Plain torch on the device."""
         Hm, Wm = _pair("hw", hw)
-        b = self.box if index is None else self.box[_tensor("index", index, (torch.int32, torch.int64), "int32 or int64", (None,)).long()]
+        b = self.box if index is None else self.box[_A.tensor("index", index, (torch.int32, torch.int64), "int32 or int64", (None,)).long()]
         x0 = torch.div(b[:, 0] + b[:, 2] + 1 - Wm, 2, rounding_mode="floor")
         y0 = torch.div(b[:, 1] + b[:, 3] + 1 - Hm, 2, rounding_mode="floor")
         return torch.where(b[:, :1] < 0, torch.zeros_like(b[:, :2]), torch.stack((x0, y0), 1)).to(torch.int32)
@@ -314,21 +276,19 @@ def decode(store, index=None, origin_xy=None, hw=None, out=None):
         hw = store.frame_hw
     Hm, Wm = _pair("hw", hw)
     if index is not None:
-        _tensor("index", index, (torch.int32,), "int32", (None,))
+        _A.tensor("index", index, (torch.int32,), "int32", (None,))
     B = store.F if index is None else int(index.shape[0])
     if origin_xy is not None:
-        _tensor("origin_xy", origin_xy, (torch.int32, torch.int64), "int32 or int64", (B, 2))
+        _A.tensor("origin_xy", origin_xy, (torch.int32, torch.int64), "int32 or int64", (B, 2))
     dev = store.device
     if out is not None:
         if not isinstance(out, (tuple, list)) or len(out) != 2:
             raise ValueError("lc_amd.rle: out is the pair (masks, info)")
-        _tensor("out[0]", out[0], (torch.uint8,), "uint8", (B, Hm, Wm))
-        _tensor("out[1]", out[1], (torch.int32,), "int32", (B,))
+        _A.tensor("out[0]", out[0], (torch.uint8,), "uint8", (B, Hm, Wm))
+        _A.tensor("out[1]", out[1], (torch.int32,), "int32", (B,))
         if not (out[0].is_contiguous() and out[1].is_contiguous()):
             raise ValueError("lc_amd.rle: out must be contiguous")
-    for name, t in (("index", index), ("origin_xy", origin_xy), *((f"out[{i}]", t) for i, t in enumerate(out or ()))):
-        if t is not None and t.device != dev:
-            raise RuntimeError(f"lc_amd.rle: {name} is on {t.device}, the store on {dev}")
+    _A.same_device(dev, "the store on {}", index=index, origin_xy=origin_xy, **{f"out[{i}]": t for i, t in enumerate(out or ())})
     idx = None if index is None else index.contiguous()
     org = None if origin_xy is None else origin_xy.to(torch.int32).contiguous()
     masks, info = out if out is not None else (torch.empty((B, Hm, Wm), device=dev, dtype=torch.uint8), torch.empty((B,), device=dev, dtype=torch.int32))
@@ -338,7 +298,7 @@ def decode(store, index=None, origin_xy=None, hw=None, out=None):
             rc = lib.lc_rle_decode_u8(_lib.ptr(store.ends), _lib.ptr(store.offsets), _lib.ptr(store.sizes), _lib.ptr(store.valid), store.T, store.F, _lib.ptr(idx),
                                       _lib.ptr(org), B, Hm, Wm, _lib.ptr(masks), _lib.ptr(info), _lib.stream_ptr(dev))
         if rc != 0:
-            _fail(lib, "decode", rc)
+            _SO.fail("rle.decode", rc)
     return masks, info
 
 
@@ -347,32 +307,30 @@ def encode(masks, sizes=None, origin_xy=None, cap=1024, out=None) -> Encoded:
     """masks (F,Hm,Wm) uint8 or bool on the device (non-zero = set; `GtInfo.mask_visib` as it is), each a window at origin_xy[f] ((F,2)
     int32 / int64 or None: (0,0)) of a frame of sizes[f] ((F,2) int32 tensor, a pair (H, W) for all, or None: the window is the frame).
     Frame pixels outside the window are 0; window pixels outside the frame are ignored.  -> Encoded: the canonical lists in (F,cap)."""
-    masks = _tensor("masks", masks, (torch.uint8, torch.bool), "uint8 or bool", (None, None, None))
+    masks = _A.tensor("masks", masks, (torch.uint8, torch.bool), "uint8 or bool", (None, None, None))
     F, Hm, Wm = (int(v) for v in masks.shape)
     if not (1 <= Hm <= MAX_SIZE and 1 <= Wm <= MAX_SIZE):
         raise ValueError(f"lc_amd.rle: mask sizes of 1 to {MAX_SIZE}, got {Hm} x {Wm}")
-    cap = _whole("cap", cap, 1, 2 ** 31 - 1)
+    cap = _A.whole("cap", cap, 1, 2 ** 31 - 1, numpy=True)
     if sizes is not None and not isinstance(sizes, Tensor):
         sizes = torch.from_numpy(np.tile(np.asarray(_pair("sizes", sizes), dtype=np.int32), (F, 1)))
         sizes = sizes.to(masks.device) if masks.is_cuda else sizes
     if sizes is not None:
-        _tensor("sizes", sizes, (torch.int32,), "int32", (F, 2))
+        _A.tensor("sizes", sizes, (torch.int32,), "int32", (F, 2))
     if origin_xy is not None:
-        _tensor("origin_xy", origin_xy, (torch.int32, torch.int64), "int32 or int64", (F, 2))
+        _A.tensor("origin_xy", origin_xy, (torch.int32, torch.int64), "int32 or int64", (F, 2))
     if out is not None:
         if not isinstance(out, (tuple, list)) or len(out) != 3:
             raise ValueError("lc_amd.rle: out is the triple (counts, n_runs, info)")
-        _tensor("out[0]", out[0], (torch.int32,), "int32", (F, cap))
-        _tensor("out[1]", out[1], (torch.int32,), "int32", (F,))
-        _tensor("out[2]", out[2], (torch.int32,), "int32", (F,))
+        _A.tensor("out[0]", out[0], (torch.int32,), "int32", (F, cap))
+        _A.tensor("out[1]", out[1], (torch.int32,), "int32", (F,))
+        _A.tensor("out[2]", out[2], (torch.int32,), "int32", (F,))
         if not all(t.is_contiguous() for t in out):
             raise ValueError("lc_amd.rle: out must be contiguous")
     if not masks.is_cuda:
         raise RuntimeError(f"lc_amd.rle: masks is on {masks.device}; the HIP path needs tensors on the MI355X (there is no CPU fallback in the product path)")
     dev = masks.device
-    for name, t in (("sizes", sizes), ("origin_xy", origin_xy), *((f"out[{i}]", t) for i, t in enumerate(out or ()))):
-        if t is not None and t.device != dev:
-            raise RuntimeError(f"lc_amd.rle: {name} is on {t.device}, the masks on {dev}")
+    _A.same_device(dev, "the masks on {}", sizes=sizes, origin_xy=origin_xy, **{f"out[{i}]": t for i, t in enumerate(out or ())})
     masks = masks.contiguous()
     m8 = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
     siz = None if sizes is None else sizes.contiguous()
@@ -384,5 +342,5 @@ def encode(masks, sizes=None, origin_xy=None, cap=1024, out=None) -> Encoded:
         with _lib.on_device(dev):
             rc = lib.lc_rle_encode_u8(_lib.ptr(m8), F, Hm, Wm, _lib.ptr(siz), _lib.ptr(org), cap, _lib.ptr(counts), _lib.ptr(n_runs), _lib.ptr(info), _lib.stream_ptr(dev))
         if rc != 0:
-            _fail(lib, "encode", rc)
+            _SO.fail("rle.encode", rc)
     return Encoded(counts, n_runs, info)

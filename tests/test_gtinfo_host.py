@@ -1,4 +1,4 @@
-"""The ground-truth annotations without a GPU: the library of its own (liblc_amd_gtinfo.so: build group and order, header, exports,
+"""The ground-truth annotations without a GPU: the library of its own (liblc_amd_gtinfo.so: place in the registry and build order, header, exports,
 signatures and source hash agree; no other library sees its sources), every refusal of the wrappers (lc_amd.gtinfo) on CPU tensors, the
 argument checks of the two C entry points before any launch, the kernels' resources read from the code object, and `bop_records`."""
 import ctypes
@@ -18,14 +18,12 @@ def test_build_group_and_order(monkeypatch):
     import __graft_entry__ as entry
     from lc_amd import build
 
-    assert build.annot_targets() == (build.GTINFO,)
-    earlier = build.all_targets() + build.tool_targets() + build.eval_targets() + build.scene_targets()
-    assert len(earlier) == 8 and build.GTINFO not in earlier
+    assert build.TARGETS.index(build.GTINFO) == 8 and build.TARGETS.count(build.GTINFO) == 1  # ninth, after the eight before it
     assert build.GTINFO.so_path.endswith(os.path.join("_C", "liblc_amd_gtinfo.so")) and build.GTINFO.header == "lc_amd_gtinfo.h" and build.GTINFO.shared == (build.RAY_LENGTH_H, build.WAVE_INT_H)
     asked, real = [], build.build
     monkeypatch.setattr(build, "build", lambda force=False, verbose=False, target=build.MAIN: (asked.append(target), real(force, verbose, target))[1])
     entry.build()
-    assert tuple(asked[:9]) == earlier + build.annot_targets()  # built ninth
+    assert tuple(asked[:9]) == build.TARGETS[:9] and asked.index(build.GTINFO) == build.TARGETS.index(build.GTINFO)  # built ninth
     assert os.path.exists(build.GTINFO.so_path) and not build.is_stale(build.GTINFO)
     doc = build.__doc__
     assert "liblc_amd_gtinfo.so" in doc and "lc_amd/csrc/gtinfo/" in doc and "include/lc_amd_gtinfo.h" in doc
@@ -65,7 +63,8 @@ def test_source_hash_is_its_own():
     assert not build.is_stale(T)
     assert lib.lc_amd_gtinfo_source_hash().decode() == build.source_hash(T) == build.embedded_hash(T.so_path, T.hash_marker)
     assert build.sources(T) == [os.path.join(build.CSRC, "gtinfo", "lc_gtinfo.hip")]
-    others = build.all_targets() + build.tool_targets() + build.eval_targets() + build.scene_targets()
+    others = [t for t in build.TARGETS if t is not T]
+    assert len(others) == 11
 
     def mine(d):
         return os.sep + "gtinfo" + os.sep in d or d.endswith("lc_amd_gtinfo.h")

@@ -425,14 +425,15 @@ def test_training_shape_fixtures_span_the_warm_up_ramp_and_the_reference_shapes(
             assert tuple(out["pts2d"].shape) == (256, 64, 2) and z["s0_grad_pts2d"].shape == (256, 64, 2)
 
 
-@pytest.mark.parametrize("name", ["main", "crop"])
+@pytest.mark.parametrize("name", ["main", "optim", "posecov", "render", "crop", "models", "symerr", "vsd", "gtinfo", "maskcrop", "augment", "rle"])
 def test_shared_loader_refuses_what_it_cannot_rebuild(name, tmp_path, monkeypatch):
     """The refusal branches of the one loader behind every module's load(), without a compiler run and without a dlopen: a library built
-    from other sources on a box without hipcc, and a missing library where building is not wanted.  Two targets: the messages name the
-    paths and the hashes of the target they were given."""
+    from other sources on a box without hipcc, and a missing library where building is not wanted.  Every target of the registry: the
+    messages name the paths and the hashes of the target they were given."""
     from lc_amd import _lib, build
 
-    target = next(t for t in build.all_targets() if t.name == name)._replace(so_path=str(tmp_path / f"lib_{name}.so"))
+    assert [t.name for t in build.TARGETS].count(name) == 1
+    target = next(t for t in build.TARGETS if t.name == name)._replace(so_path=str(tmp_path / f"lib_{name}.so"))
     monkeypatch.setattr(build, "hipcc_available", lambda: False)
     monkeypatch.setattr(build, "build", lambda *a, **k: pytest.fail("the loader must not try to build here"))
     monkeypatch.delenv("LC_AMD_ALLOW_STALE", raising=False)
@@ -447,8 +448,8 @@ def test_shared_loader_refuses_what_it_cannot_rebuild(name, tmp_path, monkeypatc
         assert msg.startswith(f"lc_amd: {target.so_path} was built from other sources than the ones next to it (embedded hash None, "
                               f"sources {build.source_hash(target)}) and hipcc is not available")
         assert msg.endswith("set LC_AMD_ALLOW_STALE=1 to load it as it is")
-    others = {build.source_hash(t) for t in build.all_targets() if t.name != name}
-    assert not any(h in msg for h in others)
+    others = {build.source_hash(t) for t in build.TARGETS if t.name != name}
+    assert len(others) == 11 and not any(h in msg for h in others)
 
 
 def test_every_build_switch_is_listed_in_the_design():

@@ -1,7 +1,7 @@
 """What the main library's registries check, for liblc_amd_models.so (no GPU needed): every compiled kernel form is named in
 tests/launch_forms_models.py with the GPU tests that launch it and every entry still names a form and existing tests
 (tests/test_launch_forms.py does this for liblc_amd.so only); the kernels' registers, LDS and scratch (tests/test_kernel_resources.py);
-and the shared loader's refusals for this target (tests/test_host_logic.py runs them over `build.all_targets()`)."""
+and the shared loader's refusals for this target (tests/test_host_logic.py runs them over every name of `build.TARGETS`)."""
 import ast
 import os
 import re
@@ -78,7 +78,8 @@ def test_shared_loader_refuses_what_it_cannot_rebuild(tmp_path, monkeypatch):
         msg = str(e.value)
         assert msg.startswith(f"lc_amd: {target.so_path} was built from other sources than the ones next to it (embedded hash None, "
                               f"sources {build.source_hash(build.MODELS)}) and hipcc is not available")
-    assert not any(build.source_hash(t) in msg for t in build.all_targets())
+    assert not any(build.source_hash(t) in msg for t in build.TARGETS if t is not build.MODELS)
+    assert len([t for t in build.TARGETS if t is not build.MODELS]) == 11
 
 
 def test_source_hash_covers_the_shared_cross_lane_header():

@@ -37,10 +37,12 @@ def test_embedded_source_hash_and_separate_sources():
     lib = posecov.load()
     assert lib.lc_amd_posecov_source_hash().decode() == build.source_hash(build.POSECOV) == build.embedded_hash(build.POSECOV.so_path, build.POSECOV.hash_marker)
     assert build.sources(build.POSECOV) == [os.path.join(build.CSRC, "posecov", "lc_pose_cov.hip")]
-    for t in (t for t in build.all_targets() if t is not build.POSECOV):  # no other library sees this directory or header
+    others = [t for t in build.TARGETS if t is not build.POSECOV]
+    assert len(others) == 11
+    for t in others:  # no other library sees this directory or header
         assert not any("posecov" in os.path.relpath(s, ROOT) for s in build._deps(t))
-    assert build.all_targets() == (build.MAIN, build.OPTIM, build.POSECOV, build.RENDER, build.CROP)
-    assert len({build.source_hash(t) for t in build.all_targets()}) == 5
+    assert build.TARGETS[:5] == (build.MAIN, build.OPTIM, build.POSECOV, build.RENDER, build.CROP)
+    assert len({build.source_hash(t) for t in build.TARGETS}) == 12
 
 
 def _quoted_includes(path):
@@ -55,9 +57,8 @@ def test_every_library_hashes_every_file_it_includes(tmp_path, monkeypatch):
 
     from lc_amd import build
 
-    every = build.every_target()
-    assert every == (build.all_targets() + build.tool_targets() + build.eval_targets() + build.scene_targets() + build.annot_targets() +
-                     build.loader_targets()) and len(every) == 10
+    every = build.TARGETS
+    assert len(every) == 12 and len(set(every)) == 12
     for t in every:
         deps = {os.path.normpath(d) for d in build._deps(t)}
         assert all(os.path.exists(d) for d in deps), t.name
@@ -70,10 +71,12 @@ def test_every_library_hashes_every_file_it_includes(tmp_path, monkeypatch):
             assert f in deps, f"{t.name}: {f} is included but not hashed"
             todo += _quoted_includes(f)
     shared = os.path.join(build.CSRC, "shared", "lc_shared.h")
-    assert [t for t in build.all_targets() if shared in build._deps(t)] == [build.MAIN, build.POSECOV]
-    assert shared in _quoted_includes(os.path.join(build.CSRC, "lc_common.h")) and shared in _quoted_includes(build.sources(build.POSECOV)[0])
+    users = [build.MAIN, build.POSECOV, build.MODELS, build.SYMERR]
+    assert [t for t in every if shared in build._deps(t)] == users == [t for t in every if build.SHARED_H in t.shared] and shared == build.SHARED_H
+    assert shared in _quoted_includes(os.path.join(build.CSRC, "lc_common.h"))
+    assert all(shared in _quoted_includes(build.sources(t)[0]) for t in users[1:])
 
-    # one more byte in the shared header of a COPY of the sources: exactly those two hashes change
+    # one more byte in the shared header of a COPY of the sources: exactly those four hashes change
     pkg = tmp_path / "lc_amd"
     shutil.copytree(build.CSRC, pkg / "csrc")
     shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "include")
@@ -82,13 +85,13 @@ def test_every_library_hashes_every_file_it_includes(tmp_path, monkeypatch):
     def moved(path):
         return str(pkg / os.path.relpath(path, os.path.dirname(build.CSRC)))
 
-    copies = [t._replace(src_dir=moved(t.src_dir), shared=tuple(moved(s) for s in t.shared)) for t in build.all_targets()]
+    copies = [t._replace(src_dir=moved(t.src_dir), shared=tuple(moved(s) for s in t.shared)) for t in every]
     before = [build.source_hash(t) for t in copies]
-    assert before == [build.source_hash(t) for t in build.all_targets()]  # (names and contents: the copy hashes like the tree)
+    assert before == [build.source_hash(t) for t in every]  # (names and contents: the copy hashes like the tree)
     with open(moved(shared), "ab") as f:
         f.write(b"\n")
     after = [build.source_hash(t) for t in copies]
-    assert [t.name for t, x, y in zip(copies, before, after) if x != y] == ["main", "posecov"]
+    assert [t.name for t, x, y in zip(copies, before, after) if x != y] == ["main", "posecov", "models", "symerr"]
 
     # the same for the headers of the image libraries, over every library: one more byte changes exactly the hashes of those that include it
     copies = [t._replace(src_dir=moved(t.src_dir), shared=tuple(moved(s) for s in t.shared)) for t in every]

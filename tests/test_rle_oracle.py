@@ -140,13 +140,13 @@ def test_build_group_header_exports_and_source_hash(monkeypatch):
     from lc_amd import build, rle
 
     T = build.RLE
-    assert build.mask_store_targets() == (T,) and T not in build.every_target() + build.augment_targets()
-    assert len(build.every_target()) == 10 and build.augment_targets() == (build.AUGMENT,)
+    others = [t for t in build.TARGETS if t is not T]
+    assert build.TARGETS[11] is T and len(others) == 11 and build.TARGETS[10] is build.AUGMENT and len(build.TARGETS[:10]) == 10
     assert T.so_path.endswith(os.path.join("_C", "liblc_amd_rle.so")) and T.header == "lc_amd_rle.h" and T.shared == ()
     asked, real = [], build.build
     monkeypatch.setattr(build, "build", lambda force=False, verbose=False, target=build.MAIN: (asked.append(target), real(force, verbose, target))[1])
     entry.build()
-    assert tuple(asked[:12]) == build.every_target() + build.augment_targets() + (T,)  # built twelfth
+    assert tuple(asked[:12]) == build.TARGETS and asked.index(T) == build.TARGETS.index(T) == 11  # built twelfth
     monkeypatch.undo()
     lib = rle.load()
     assert not build.is_stale(T)
@@ -156,7 +156,7 @@ def test_build_group_header_exports_and_source_hash(monkeypatch):
     def mine(d):
         return os.sep + "rle" + os.sep in d or d.endswith("lc_amd_rle.h")
 
-    for t in build.every_target() + build.augment_targets():  # no other library sees this directory or header, or carries this marker
+    for t in others:  # no other library sees this directory or header, or carries this marker
         assert not any(mine(d) for d in build._deps(t)), t.name
         assert build.embedded_hash(t.so_path, T.hash_marker) is None, t.name
     assert all(mine(d) for d in build._deps(T))
