@@ -54,6 +54,38 @@
  * B = 0 launches nothing.  One launch on `stream` (hipStream_t as void*): no workspace, no allocation, no wait, capturable in a
  * hipGraph.  Every output is defined bit for bit: the same for any batch, order and grid shape.  0 on success, else
  * lc_amd_augment_last_error().
+ *
+ * lc_augment_drawn_u8 is the same launch with the rows DRAWN BY THE KERNEL: neither `params` nor `lut` exists on the host.  The first
+ * wavefront of every workgroup forms its own sample's row from (cfg, seed, sample_id, h, w) before the pixel work and hands it on where
+ * lc_augment_u8 stages what it read; the row is then judged and used exactly as above.  It is the row `draw` of lc_amd/augment.py makes:
+ *   u(op, i) = (key(op, i) >> 8) / 2^24 in fp64, with the host op codes LC_AUGMENT_OP_SWITCH ... LC_AUGMENT_OP_CONTRAST below
+ *   switch   = u(SWITCH, 0) < switch_bg_prob and n_backgrounds > 0;  P[1] = min(trunc(u(SWITCH, 1) n_backgrounds), n_backgrounds - 1)
+ *   chain    = u(CHAIN, 0) < pixel_aug_prob: the gate in front of every stage below
+ *   salt     = use_peper_salt and u(SALT, 0) < 0.3;  P[2] = floor(0.05 2^32)
+ *   motion   = use_motion_blur and u(MOTION, 0) < 0.2;  angle = 360 u(MOTION, 1) degrees, direction d = 2 u(MOTION, 2) - 1;  P[6..30]: five
+ *              taps at s = -2..2 along (sin t, -cos t) from the centre, weighted (1 - d) / 2 + (s + 2) d / 4, each splatted bilinearly
+ *   dropout  = u(DROPOUT, 0) < 0.5;  P[3] = floor(0.1 2^32), P[4] = max(1, 5 h / 100), P[5] = max(1, 5 w / 100) in integer division
+ *   gauss    = u(GAUSS, 0) < 0.5 and sigma >= 1e-3, sigma = 1.2 u(GAUSS, 1);  P[31..55]: g_i = exp(-i^2 / 2 sigma^2), i = -2..2, normalised,
+ *              the outer product
+ *   add, invert, multiply per channel, multiply, contrast: gates u(op, 0) < 0.5, 0.4 (and use_invert), 0.5, 0.5, 0.5; bit 5 is set when
+ *              one of them is open.  A per-channel value is u(op, 2 + c) where u(op, 1) < 0.3 (ADD, CONTRAST) or 0.5 (MUL_PC), else
+ *              u(op, 2) for all three; channel c is inverted where u(INVERT, 1 + c) < 0.2.  The table of channel c is the composition, in
+ *              this order, of  v + min(-25 + floor(51 u), 25),  255 - v,  v (0.6 + 0.8 u),  v (0.6 + 0.8 u),  128 + (0.5 + 1.7 u)(v - 128),
+ *              every step clip(rint(.), 0, 255) in fp64, every product and sum rounded on its own (nothing fused)
+ *   words of a stage whose gate is shut are 0, and the table of a row without bit 5 is the identity.
+ * Bits, the background, the grid and the tables are EQUAL to `draw`'s, bit for bit.  A filter's 25 fp64 weights pass through
+ * floor(x 65536 + 1/2) with the remainder to 65536 added to the centre; exp, sin and cos are polynomials of this library on a reduced
+ * argument (the quadrant of the angle is taken from the integer key), not the host's math library, so each Q16 weight is within 1 of
+ * `draw`'s, each is >= 0 and each set sums to exactly 65536.
+ *   cfg: by value; the probabilities must lie in [0, 1]; 0 <= n_backgrounds <= G (a row names backgrounds 0 .. n_backgrounds - 1)
+ *   seed: a DEVICE pointer to one uint64, aligned to 8 bytes, read by the kernel: a replayed graph draws anew once the word has changed.
+ *      The salt and the dropout of the pixels use the same word.
+ *   sample_id (B) int32: required
+ *   params_out (B,64) int32 and lut_out (B,3,256) uint8, each or both NULL: the rows as drawn (before they are judged: a row that
+ *      switches the background without msk_in is drawn, written here, and refused with info = -1), written by the drawing wavefront
+ *   form: there is no argument.  The launch takes LC_AUGMENT_FILTERED unless cfg rules every filter out, which is pixel_aug_prob = 0
+ *      (both filters stand behind the chain's gate, and the Gaussian behind no switch of cfg); then it takes LC_AUGMENT_POINTWISE.
+ *   everything else -- crops, backgrounds, msk_in, out_dtype, mean, std, out, info, the sizes, alignment, B = 0, stream -- as above.
  */
 #ifndef LC_AMD_AUGMENT_H
 #define LC_AMD_AUGMENT_H
@@ -77,6 +109,30 @@
 #define LC_AUGMENT_OP_SNPV 65538
 #define LC_AUGMENT_OP_DROP 65539
 #define LC_AUGMENT_OP_HOST 131072
+/* the host's decisions, one op code each (lc_amd/augment.py: OP_*); the index i of u(op, i) tells the draws of one decision apart */
+#define LC_AUGMENT_OP_SWITCH 131073
+#define LC_AUGMENT_OP_CHAIN 131074
+#define LC_AUGMENT_OP_SALT 131075
+#define LC_AUGMENT_OP_MOTION 131076
+#define LC_AUGMENT_OP_DROPOUT 131077
+#define LC_AUGMENT_OP_GAUSS 131078
+#define LC_AUGMENT_OP_ADD 131079
+#define LC_AUGMENT_OP_INVERT 131080
+#define LC_AUGMENT_OP_MUL_PC 131081
+#define LC_AUGMENT_OP_MUL 131082
+#define LC_AUGMENT_OP_CONTRAST 131083
+#define LC_AUGMENT_OP_BG_REGION 131084
+#define LC_AUGMENT_OP_ZOOM 131085
+
+/* what `draw` reads of AugmentConfig, and the number of backgrounds it may name */
+typedef struct lc_augment_draw_config {
+    double pixel_aug_prob;
+    double switch_bg_prob;
+    int use_peper_salt;
+    int use_motion_blur;
+    int use_invert;
+    int n_backgrounds;
+} lc_augment_draw_config;
 
 #ifdef __cplusplus
 extern "C" {
@@ -89,6 +145,10 @@ const char *lc_amd_augment_source_hash(void);
 int lc_augment_u8(const unsigned char *crops, const unsigned char *backgrounds, int G, const float *msk_in, const int *params,
                   const unsigned char *lut, int B, int h, int w, uint64_t seed, const int *sample_id, int out_dtype, int form,
                   const float *mean, const float *std, void *out, int *info, void *stream);
+
+int lc_augment_drawn_u8(const unsigned char *crops, const unsigned char *backgrounds, int G, const float *msk_in,
+                        lc_augment_draw_config cfg, const uint64_t *seed, const int *sample_id, int B, int h, int w, int out_dtype,
+                        const float *mean, const float *std, void *out, int *info, int *params_out, unsigned char *lut_out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,8 @@ does per instance on a host core with the warped crop (`dataset.py:137-148,413-4
     draw(cfg, seed, sample_ids, n_backgrounds, hw=(256, 256)) -> params (B,64) int32, lut (B,3,256) uint8      host numpy, no device
     augment(crops, params, lut, *, msk_in=None, backgrounds=None, seed=0, sample_id=None, dtype=torch.float32, normalize=None,
             pointwise=None) -> (out, info)
+    augment_drawn(crops, cfg, *, seed, sample_id, msk_in=None, backgrounds=None, dtype=torch.float32, normalize=None,
+                  return_rows=False) -> (out, info[, params, lut])      the same launch with its rows drawn by the kernel
     background_matrices(seed, sample_ids, bg_hw, out_hw) -> (B,2,3) float32 for `crops.warp_affine`
     draw_zoom(cfg, seed, sample_ids, bbox_xyxy, im_hw) -> centre (B,2), scale (B,), rotation (B,) for `crops.affine_from_box`
 
@@ -18,12 +20,14 @@ with OpenCV's BORDER_REFLECT_101, the point operations one 256-entry table per c
 
 HIP tensors only (anything else raises: there is no CPU fallback).  Runs on the current stream, never waits for the device, needs no
 workspace and -- with `params` and `lut` already on the device -- allocates its outputs only and can be captured into a graph.
+`augment_drawn` needs no `draw` on the host at all: the kernel forms each sample's row from (cfg, a seed word on the device, sample_id), so
+a captured graph draws anew at every replay once that word has changed.
 """
 from __future__ import annotations
 
 import ctypes
 import math
-from ctypes import c_int, c_uint64, c_void_p
+from ctypes import c_double, c_int, c_uint64, c_void_p
 from dataclasses import dataclass
 
 import numpy as np
@@ -261,8 +265,15 @@ def draw_zoom(cfg: AugmentConfig, seed, sample_ids, bbox_xyxy, im_hw):
     return centre, scale, rot
 
 
+class DrawConfig(ctypes.Structure):
+    """lc_augment_draw_config, by value: what `draw` reads of an AugmentConfig, and the number of backgrounds a row may name."""
+    _fields_ = [("pixel_aug_prob", c_double), ("switch_bg_prob", c_double), ("use_peper_salt", c_int), ("use_motion_blur", c_int),
+                ("use_invert", c_int), ("n_backgrounds", c_int)]
+
+
 _SO = _lib.SideLibrary(_build.AUGMENT, {
     "lc_augment_u8": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 3 + [c_int] * 3 + [c_uint64, c_void_p, c_int, c_int, _FLOATS, _FLOATS] + [c_void_p] * 3),
+    "lc_augment_drawn_u8": (c_int, [c_void_p, c_void_p, c_int, c_void_p, DrawConfig, c_void_p, c_void_p] + [c_int] * 4 + [_FLOATS, _FLOATS] + [c_void_p] * 5),
 })
 _SIGNATURES, load = _SO.signatures, _SO.load
 _A = _args.Args("augment")  # its whole numbers may be numpy's (`whole(..., numpy=True)`): seeds and sizes come out of arrays here
@@ -363,3 +374,83 @@ def augment(crops, params, lut, *, msk_in=None, backgrounds=None, seed=0, sample
         if rc != 0:
             _SO.fail("augment.augment", rc)
     return out, info
+
+
+def _seed_word(seed, dev) -> Tensor:
+    """The seed as one 64-bit word on the device.  A whole number is written there by a fill (no host copy, no wait: capturable); a
+    tensor is the caller's own word, which the kernel reads at every launch and replay."""
+    if isinstance(seed, Tensor):
+        if seed.dtype not in (torch.uint64, torch.int64) or seed.numel() != 1:
+            raise TypeError(f"lc_amd.augment: a seed tensor holds one uint64 or int64 element, got {seed.dtype} of shape {tuple(seed.shape)}")
+        if seed.device != dev:
+            raise RuntimeError(f"lc_amd.augment: seed is on {seed.device}, the crops on {dev}")
+        return seed
+    seed = _A.whole("seed", seed, 0, 2 ** 64 - 1, numpy=True)
+    return torch.full((1,), seed - 2 ** 64 if seed >= 2 ** 63 else seed, dtype=torch.int64, device=dev)  # the same 64 bits
+
+
+@torch.no_grad()
+def augment_drawn(crops, cfg: AugmentConfig, *, seed, sample_id, msk_in=None, backgrounds=None, dtype=torch.float32, normalize=None, return_rows=False):
+    """`augment(crops, *draw(cfg, seed, sample_id, G, (h, w)), msk_in=..., backgrounds=..., seed=seed, sample_id=sample_id, ...)` with the
+    rows drawn by the kernel (`lc_augment_drawn_u8` of include/lc_amd_augment.h): `params` and `lut` never exist on the host.  G is
+    the number of `backgrounds` (0 without them: no row switches).  The bits, the background, the dropout grid and the tables are
+    `draw`'s bit for bit; each Q16 filter weight is within 1 of `draw`'s (the device has its own exp, sin and cos), non-negative, and
+    each set sums to 65536.
+
+    seed: a whole number below 2^64, or a device tensor of one uint64 / int64 element that the KERNEL reads: a captured graph draws anew
+    at every replay once the caller has changed that word (`seed_word.add_(1)`, or a copy into it).  sample_id (B,) int32 is required:
+    a drawn row belongs to its sample, not to its place in the batch.  A row that switches the background while `msk_in` is None is
+    refused as `augment` refuses it on device params: info = -1, the unchanged crop.
+
+    The launch takes the filtered form unless `cfg.pixel_aug_prob == 0`, which rules both filters out.  Allocates its outputs only
+    (and the one word of a by-value seed), never waits for the device, and can be captured into a graph.
+
+    -> (out, info) as `augment`; with `return_rows` also (params (B,64) int32, lut (B,3,256) uint8) on the device: the rows as drawn."""
+    crops = _A.tensor("crops", crops, (torch.uint8,), "uint8", (None, 3, None, None))
+    B, _, h, w = (int(s) for s in crops.shape)
+    if not (MIN_SIZE <= h <= MAX_SIZE and MIN_SIZE <= w <= MAX_SIZE):
+        raise ValueError(f"lc_amd.augment: crop sizes of {MIN_SIZE} to {MAX_SIZE}, got {h} x {w}")
+    if not isinstance(cfg, AugmentConfig):
+        raise TypeError(f"lc_amd.augment: cfg must be an AugmentConfig, got {type(cfg)}")
+    for name in ("pixel_aug_prob", "switch_bg_prob"):
+        if not 0.0 <= float(getattr(cfg, name)) <= 1.0:
+            raise ValueError(f"lc_amd.augment: {name} must lie in [0, 1], got {getattr(cfg, name)}")
+    if sample_id is None:
+        raise TypeError("lc_amd.augment: augment_drawn needs sample_id: a drawn row belongs to its sample")
+    _A.tensor("sample_id", sample_id, (torch.int32,), "int32", (B,))
+    if msk_in is not None:
+        _A.tensor("msk_in", msk_in, (torch.float32,), "float32", (B, h, w))
+    if backgrounds is not None:
+        _A.tensor("backgrounds", backgrounds, (torch.uint8,), "uint8", (None, 3, h, w))
+    if dtype not in OUT_DTYPES:
+        raise TypeError(f"lc_amd.augment: dtype must be one of uint8, float32, float16, bfloat16, got {dtype}")
+    mean = std = None
+    if normalize is not None:
+        if dtype == torch.uint8:
+            raise TypeError("lc_amd.augment: normalize needs a float dtype")
+        mean, std = _A.host_floats("mean", normalize[0], 3), _A.host_floats("std", normalize[1], 3)
+    if not isinstance(seed, Tensor):
+        _A.whole("seed", seed, 0, 2 ** 64 - 1, numpy=True)
+    if not crops.is_cuda:
+        raise RuntimeError(f"lc_amd.augment: crops is on {crops.device}; the HIP path needs tensors on the MI355X (there is no CPU fallback in the product path)")
+    dev = crops.device
+    _A.same_device(dev, "the crops on {}", msk_in=msk_in, backgrounds=backgrounds, sample_id=sample_id)
+    word = _seed_word(seed, dev)
+    G = 0 if backgrounds is None else int(backgrounds.shape[0])
+    crops, sid = crops.contiguous(), sample_id.contiguous()
+    msk = None if msk_in is None else msk_in.contiguous()
+    bg = None if G == 0 else backgrounds.contiguous()
+    out = torch.empty(B, 3, h, w, device=dev, dtype=dtype)
+    info = torch.empty(B, device=dev, dtype=torch.int32)
+    params = torch.empty(B, WORDS, device=dev, dtype=torch.int32) if return_rows else None
+    lut = torch.empty(B, 3, 256, device=dev, dtype=torch.uint8) if return_rows else None
+    if B:
+        c = DrawConfig(float(cfg.pixel_aug_prob), float(cfg.switch_bg_prob), int(bool(cfg.use_peper_salt)), int(bool(cfg.use_motion_blur)),
+                       int(bool(cfg.use_invert)), G)
+        lib = load()
+        with _lib.on_device(dev):
+            rc = lib.lc_augment_drawn_u8(_lib.ptr(crops), _lib.ptr(bg), G, _lib.ptr(msk), c, _lib.ptr(word), _lib.ptr(sid), B, h, w, OUT_DTYPES[dtype],
+                                         mean, std, _lib.ptr(out), _lib.ptr(info), _lib.ptr(params), _lib.ptr(lut), _lib.stream_ptr(dev))
+        if rc != 0:
+            _SO.fail("augment.augment_drawn", rc)
+    return (out, info, params, lut) if return_rows else (out, info)
