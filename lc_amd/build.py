@@ -13,13 +13,17 @@
     maskcrop lc_amd/_C/liblc_amd_maskcrop.so lc_amd/csrc/maskcrop/    include/lc_amd_maskcrop.h the training mask crops: warps, valid count, check points
     augment  lc_amd/_C/liblc_amd_augment.so  lc_amd/csrc/augment/     include/lc_amd_augment.h  the training crops' background switch and colour augmentation
     rle      lc_amd/_C/liblc_amd_rle.so      lc_amd/csrc/rle/         include/lc_amd_rle.h      the store of COCO run-length masks: index, decode, encode
+    geometry lc_amd/_C/liblc_amd_geometry.so lc_amd/csrc/geometry/    include/lc_amd_geometry.h the training crops' geometry drawn from the seed word (LATE_TARGETS)
 
 A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`): code that
 two libraries need exists once there (lc_shared.h: main, posecov, models, symerr; lc_warp_grid.h: crop, maskcrop; lc_ray_length.h: vsd,
 gtinfo; lc_wave_int.h: vsd, gtinfo, maskcrop), and no side library restates another's arithmetic -- but for the five lines of the
 integer hash finaliser of the device's random numbers that augment has in common with maskcrop, and the wave scans that rle writes out
-for itself (tests/test_posecov_host.py states each shared header's users).
-`TARGETS` is every library in build order.  Every function takes the library it works on as a `Target` (default: the hot-path library)."""
+for itself (tests/test_posecov_host.py states each shared header's users); geometry restates the same five lines once more.
+There are two tuples.  `TARGETS` is the twelve libraries above geometry, in build order: the tests of each of them state its place in
+that tuple and the tuple's length, so it is closed.  A library that comes after them goes into `LATE_TARGETS`, and `ALL_TARGETS =
+TARGETS + LATE_TARGETS` is every library in build order: whoever builds, packages, hashes or compares "all of them" iterates
+`ALL_TARGETS`, the twelve first.  Every function takes the library it works on as a `Target` (default: the hot-path library)."""
 from __future__ import annotations
 
 import glob
@@ -84,8 +88,13 @@ MASKCROP = _side("maskcrop", (WARP_GRID_H, WAVE_INT_H))
 # the same five-line integer hash finaliser as maskcrop's (the per-pixel random numbers; nothing to do with source_hash)
 AUGMENT = _side("augment")
 RLE = _side("rle")  # the training loader's device-resident store of run-length masks (lc_amd.rle); includes no shared header
-# every library, in build order: whoever builds, hashes or compares "all of them" iterates this
+# the training loader's geometry drawn on the device from the seed word (lc_amd.geometry); includes no shared header: the five-line finaliser again
+GEOMETRY = _side("geometry")
+# the twelve whose places their own tests state: closed (see the docstring)
 TARGETS = (MAIN, OPTIM, POSECOV, RENDER, CROP, MODELS, SYMERR, VSD, GTINFO, MASKCROP, AUGMENT, RLE)
+LATE_TARGETS = (GEOMETRY,)  # the libraries after them
+# every library, in build order: whoever builds, hashes or compares "all of them" iterates this
+ALL_TARGETS = TARGETS + LATE_TARGETS
 HASH_MARKER = MAIN.hash_marker
 
 
@@ -240,5 +249,5 @@ def build_variant(name: str, flags, verbose: bool = False) -> str:
 
 
 if __name__ == "__main__":
-    for t in TARGETS:
+    for t in ALL_TARGETS:
         print(build(force=True, verbose=True, target=t))
