@@ -1,6 +1,8 @@
 """GPU tests of VSD (lc_amd.vsd, lc_amd/csrc/vsd/lc_vsd.hip).  The score on the oracle's depth maps: every count equal to the numpy fp64
 oracle's (tests/vsd_oracle.py), every error the same bits.  The chain render -> score: bit for bit the score of what render_depth returns,
-and within the number of pixels the two renderers disagree on of the full numpy chain.  Windows, batch shapes, graph replay, B = 0.  The
+and within the number of pixels the two renderers disagree on of the full numpy chain.  Windows, batch shapes, graph replay, B = 0.
+Synthetic maps of two to five strips per pose, windows over a strip boundary, probes on every strip edge and comparisons that sit on
+their thresholds (vsd_cases.STRIP_CASES): equal to the oracle again, in every batch shape and under graph replay.  The
 cases and the conditions that make exact equality a fair demand (tests/vsd_cases.py) are shown on the CPU by tests/test_vsd_oracle.py."""
 import functools
 
@@ -238,3 +240,115 @@ def test_empty_batch():
     assert out.counts.shape == (0, 13) and out.errors.shape == (0, 10) and out.counts.dtype == torch.int32
     out = _chain(name, slice(0, 0))
     assert out.counts.shape == (0, 13) and out.errors.shape == (0, 10) and out.info.shape == (0, 2)
+
+
+# ---- more than one strip per pose, and the comparisons on their thresholds (tests/vsd_cases.STRIP_CASES) ----
+
+
+def _shifted(a):
+    """The same values one element further into an allocation of their own: every 16-byte phase moves."""
+    t = _dev(a)
+    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=DEV)
+    buf[1:].copy_(t.reshape(-1))
+    return buf[1:].view(t.shape)
+
+
+def _call(c, shift=False):
+    from lc_amd import vsd
+
+    maps = _shifted if shift else _dev
+    out = vsd.vsd_from_depth(maps(c.depth_est), _dev(c.depth_gt), maps(c.depth_test), _dev(c.K), delta=c.delta, taus=c.taus, diameter=_dev(c.diameter),
+                             scene_index=_dev(c.scene_index), window_xy=_dev(c.origins), pixel_center=c.center)
+    return _np(out)
+
+
+@pytest.mark.parametrize("name", C.STRIP_NAMES)
+def test_strips_and_ties_equal_the_oracle(name):
+    """Two to five strips per pose, ragged and one-row last strips, both sides of w = kStripPixels, windows over a strip boundary, and the
+    tie case: counts entry for entry, errors bit for bit, refused rows -1 / NaN."""
+    c = C.strip_case(name)
+    want = C.strip_expected(name)
+    got = _call(c)
+    print(f"{name}: {c.claim[0]} strips, {c.claim[1]} rows in the last")
+    for i in range(len(c.depth_est)):
+        if c.refused(i):
+            assert (got[0][i] == -1).all() and np.isnan(got[1][i]).all(), i
+    _same(got, want[:2], name)
+
+
+def test_probes_count_one_pixel_on_every_strip_edge():
+    for h, w in C.PROBE_SHAPES:
+        for c, part in C.probe_calls(h, w):
+            counts, errors = _call(c)
+            assert np.array_equal(counts, np.tile(np.asarray([1, 1, 0, 0], np.int32), (len(part), 1))), (c.name, part, counts.tolist())
+            assert not errors.any(), (c.name, part)
+
+
+def test_same_bits_in_every_batch_shape_over_several_strips():
+    for name in (C.MULTI_STRIP_CASE, C.WINDOW_STRIP_CASE):
+        c = C.strip_case(name)
+        B = len(c.depth_est)
+        together = _call(c)
+        _same(together, C.strip_expected(name)[:2], name)
+        one_by_one = [_call(c.rows(slice(i, i + 1))) for i in range(B)]
+        _same((np.concatenate([a for a, _ in one_by_one]), np.concatenate([e for _, e in one_by_one])), together, (name, "one by one"))
+        rev = _call(c.rows(slice(None, None, -1)))
+        _same((rev[0][::-1], rev[1][::-1]), together, (name, "reversed"))
+        _same(_call(c, shift=True), together, (name, "shifted"))
+
+
+def test_windows_over_a_strip_boundary_score_as_the_full_frame():
+    """What test_windows shows at one strip: a window that holds both silhouettes scores as the frame does -- here with two strips per
+    window and five per frame."""
+    c = C.strip_case(C.WINDOW_STRIP_CASE)
+    held = list(C.WINDOW_STRIP_HELD)
+    full = C.full_frame_of(c, held)
+    assert c.claim[0] >= 2 and full.claim[0] > c.claim[0]
+    win = _call(c)
+    got = _call(full)
+    _same(got, (win[0][held], win[1][held]), "full frame")
+    assert not got[0][:, 2].any() and (got[0][:, 0] > 0).all()
+
+
+def test_graph_replay_over_three_strips():
+    from lc_amd import vsd
+
+    c = C.strip_case(C.MULTI_STRIP_CASE)
+    assert c.claim[0] == 3
+    want = C.strip_expected(c.name)[:2]
+    names = ("depth_est", "depth_gt", "depth_test", "K", "scene_index", "diameter")
+    t = {k: _dev(getattr(c, k)) for k in names}
+
+    def call():
+        return vsd.vsd_from_depth(t["depth_est"], t["depth_gt"], t["depth_test"], t["K"], delta=c.delta, taus=c.taus, diameter=t["diameter"],
+                                  scene_index=t["scene_index"], pixel_center=c.center)
+
+    _same(_np(call()), want, "eager")  # the warm call
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        call()
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        assert torch.cuda.is_current_stream_capturing()
+        out = call()
+    assert not torch.cuda.is_current_stream_capturing()
+    g.replay()
+    torch.cuda.synchronize()
+    _same(_np(out), want, "replay")
+    perm = [2, 0, 1]  # other poses written into the same tensors
+    for k in ("depth_est", "depth_gt", "scene_index"):
+        t[k].copy_(_dev(getattr(c, k))[perm])
+    for _ in range(2):
+        g.replay()
+        torch.cuda.synchronize()
+        _same(_np(out), (want[0][perm], want[1][perm]), "replay after the copy")
+    t["scene_index"][1] = len(c.depth_test)  # and a pose refused between two replays: all of its three workgroups return
+    g.replay()
+    torch.cuda.synchronize()
+    counts, errors = _np(out)
+    keep = [0, 2]
+    assert (counts[1] == -1).all() and np.isnan(errors[1]).all()
+    _same((counts[keep], errors[keep]), (want[0][perm][keep], want[1][perm][keep]), "the neighbours of a refused pose")

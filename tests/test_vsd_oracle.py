@@ -1,6 +1,8 @@
 """The VSD oracle (tests/vsd_oracle.py) and the case list (tests/vsd_cases.py) without a GPU: a hand-worked example, the identities the
 cases were built for, and the two conditions tests/test_gpu_vsd.py relies on -- every decided comparison at least 2^-30 (relative) from its
-threshold, and the render oracle's tie pixels at most 1 % of union."""
+threshold, and the render oracle's tie pixels at most 1 % of union.  For the strip and tie cases (vsd_cases.STRIP_CASES): the strip counts
+and window phases they claim, the ties shown equal as fp64 bits, and a numpy restatement of the kernel's launch (one block per pose and
+strip) under ten planted mistakes -- each changes a count of the case named for it, and nine of them change nothing on CASES."""
 import numpy as np
 import pytest
 import torch
@@ -152,3 +154,253 @@ def test_torch_statement_is_the_oracle():
     counts, errors = orc.torch_statement(cp(b.depth_est[sl]), cp(b.depth_gt[sl]), cp(b.depth_test), cp(b.K[:1]), C.DELTA, c.taus, cp(b.diameter[:1]),
                                          torch.zeros(1, dtype=torch.int32), torch.tensor([[ox, oy]], dtype=torch.int32))
     assert ref.counts[2] > 0 and np.array_equal(counts.numpy()[0], ref.counts) and np.array_equal(errors.numpy()[0].view(np.int32), ref.errors.view(np.int32))
+
+
+# ---- the launch shape and the ties: tests/vsd_cases.STRIP_CASES ----
+
+MISTAKES = {  # a planted mistake of the launch decomposition or of a comparison -> the case that is there to catch it
+    "last_row_dropped": "strip-ragged-w47",         # r1 = min(h, r0 + rps - 1): a strip ends one row early
+    "ragged_strip_dropped": "strip-ragged-w47",     # strips = max(1, h // rps)
+    "rps_from_frame_width": C.WINDOW_STRIP_CASE,    # the grid from rps(w), the kernel's row range from rps(W)
+    "ray_row_local": "strip-ragged-w47",            # the ray's y from the row's index inside its strip
+    "scene_row_local": "strip-ragged-w47",          # the scene's row from the row's index inside its strip
+    "cut_b_at_strip_end": C.WINDOW_STRIP_CASE,      # the bottom side judged at every strip's last row
+    "pose_and_strip_swapped": "strip-one-row-w64",  # strip = block / strips, b = block % strips
+    "lt_delta": C.TIE_CASE,                         # < delta
+    "gt_tau": C.TIE_CASE,                           # > tau d
+    "nan_hit": C.TIE_CASE,                          # !(d <= 0) as the hit test
+}
+# the one mistake of the list that the one-strip CASES see as well: with one strip it counts every pose of a call as pose 0
+SEEN_AT_ONE_STRIP = {"pose_and_strip_swapped"}
+
+
+def launch_counts(c: C.StripCase, mistake=None):
+    """lc_vsd.hip's launch restated in numpy: one block per (pose, strip), each counting its rows with the oracle's per-pixel predicates
+    into its pose's counts -> (B,T+3) int32, -1 on the refused rows.  `mistake` plants one entry of MISTAKES."""
+    assert mistake is None or mistake in MISTAKES
+    B, (h, w), (H, W), T = len(c.depth_est), c.window_hw, c.frame_hw, len(c.taus)
+    per_strip = C.rps(w)
+    strips = max(1, h // per_strip) if mistake == "ragged_strip_dropped" else -(-h // per_strip)
+    if mistake == "rps_from_frame_width":
+        per_strip = C.rps(W)
+    delta = float(np.float32(c.delta))
+    compare = dict(le=np.less if mistake == "lt_delta" else np.less_equal, ge=np.greater if mistake == "gt_tau" else np.greater_equal)
+    if mistake == "nan_hit":
+        compare["hit"] = lambda d: ~(d <= 0)
+    counts = np.zeros((B, T + 3), dtype=np.int64)
+    for block in range(B * strips):
+        b, strip = divmod(block, strips)
+        if mistake == "pose_and_strip_swapped":
+            strip, b = b, strip
+        if b >= B or c.refused(b):  # (past the batch the kernel would read what is not its own: here such a block counts nothing)
+            continue
+        r0, r1 = strip * per_strip, min(h, (strip + 1) * per_strip - (mistake == "last_row_dropped"))
+        if r1 <= r0:
+            continue
+        rows = np.arange(r0, r1)
+        x0, y0 = c.origin(b)
+        thr = np.asarray(c.taus, dtype=np.float32).astype(np.float64) * (1.0 if c.diameter is None else float(c.diameter[b]))
+        n = orc.ray_length(c.K[b], (h, w), (x0, y0), c.center)[rows - r0 if mistake == "ray_row_local" else rows]
+        scene = c.depth_test[c.scene_index[b], y0 + (rows - r0 if mistake == "scene_row_local" else rows), x0:x0 + w]
+        p = orc.pixels(c.depth_est[b, rows], c.depth_gt[b, rows], scene, n, delta, thr, **compare)
+        border = orc.cut_sides((h, w), (H, W), (x0, y0))[rows]
+        if mistake == "cut_b_at_strip_end" and y0 + h < H:
+            border[-1, :] = True
+        vis_g, vis_e = p.vis_gt, p.vis_est
+        counts[b] += [(vis_g | vis_e).sum(), (vis_g & vis_e).sum(), (border & p.hit).sum(), *p.costly.sum((1, 2))]
+    counts[[b for b in range(B) if c.refused(b)]] = -1
+    return counts.astype(np.int32)
+
+
+def _probe_cases():
+    return [c for shape in C.PROBE_SHAPES for c, _ in C.probe_calls(*shape)]
+
+
+def test_kernel_source_states_its_strip_size():
+    sp = C.strip_pixels()
+    assert sp >= 256 and sp % 4 == 0  # the width edges below are sp / 2, sp / 2 + 1, sp - 1, sp, sp + 1
+    assert C.rps(sp - 1) == 1 and C.rps(sp) == 1 and C.rps(sp + 1) == 1 and C.rps(sp // 2) == 2 and C.rps(sp // 2 + 1) == 1
+    assert C.rps(47) >= 6 and C.rps(64) >= 2
+
+
+@pytest.mark.parametrize("name", C.STRIP_NAMES)
+def test_strip_cases_meet_the_conditions_of_the_gpu_test(name):
+    c = C.strip_case(name)
+    counts, errors, refs = C.strip_expected(name)
+    B, (h, w), (H, W) = len(c.depth_est), c.window_hw, c.frame_hw
+    assert B <= 6 and h * w < 21000 and c.claim == C.strips_of(h, w)
+    assert c.K.shape == (B, 3, 3) and (c.K[:, 1, 0] == 0).all() and (c.K[:, 2] == (0, 0, 1)).all()
+    assert not np.isinf(c.depth_est).any() and not np.isinf(c.depth_gt).any() and not np.isinf(c.depth_test).any()
+    for b, r in enumerate(refs):
+        assert (r is None) == c.refused(b)
+        if r is not None:
+            print(f"{name} row {b}: strips {c.claim} counts {r.counts.tolist()} margin {r.margin:.3g}")
+            assert r.margin >= C.MARGIN or name == C.TIE_CASE  # (the tie case: test_tie_pixels_sit_on_their_thresholds)
+    if name == C.TIE_CASE:
+        return
+    n_strips, per_strip = c.claim[0], C.rps(w)
+    assert n_strips >= 2 and (c.K[:, 0, 0] != c.K[:, 1, 1]).all() and (c.K[:, 0, 1] != 0).all()
+    valid = [b for b in range(B) if not c.refused(b)]
+    # every strip of the case holds hits, and steps 2 to 4 decide pixels both ways
+    hit_rows = np.zeros(h, dtype=bool)
+    ways = np.zeros((3, 2), dtype=bool)
+    for b in valid:
+        x0, y0 = c.origin(b)
+        p = orc.pixels(c.depth_est[b], c.depth_gt[b], c.depth_test[c.scene_index[b], y0:y0 + h, x0:x0 + w], orc.ray_length(c.K[b], (h, w), (x0, y0), c.center),
+                       float(np.float32(c.delta)), np.asarray(c.taus, np.float32).astype(np.float64) * float(c.diameter[b]))
+        hit_rows |= p.hit.any(1)
+        asked_g, asked_e, inter = np.isfinite(p.margin_gt), np.isfinite(p.margin_est), p.vis_gt & p.vis_est
+        for i, (asked, yes) in enumerate(((asked_g, p.lhs_gt <= c.delta), (asked_e, p.lhs_est <= c.delta), (inter, p.costly[-1]))):
+            ways[i] |= [(asked & yes).any(), (asked & ~yes).any()]
+        assert (asked_e & ~(p.lhs_est <= c.delta) & p.vis_est).any()  # an estimate behind the scene that the visible gt makes visible
+        assert (p.hit & ~(c.depth_test[c.scene_index[b], y0:y0 + h, x0:x0 + w] > 0)).any()  # the missing patch lies under the hits
+    assert ways.all(), ways
+    assert all(hit_rows[s * per_strip:(s + 1) * per_strip].any() for s in range(n_strips))
+    assert hit_rows[(n_strips - 1) * per_strip:].any()
+
+
+def test_strip_case_list_reaches_every_path_the_issue_names():
+    sp = C.strip_pixels()
+    by = {c.name: c for c in C.STRIP_CASES}
+    assert by["strip-ragged-w47"].window_hw == (2 * C.rps(47) + 5, 47) and by["strip-ragged-w47"].claim == (3, 5)
+    assert by["strip-one-row-w64"].window_hw == (C.rps(64) + 1, 64) and by["strip-one-row-w64"].claim == (2, 1)
+    widths = {c.window_hw[1]: c for c in C.STRIP_CASES}
+    assert {sp // 2, sp // 2 + 1, sp - 1, sp, sp + 1} <= set(widths)
+    assert all(widths[w].window_hw[0] in (3, 5) for w in (sp // 2, sp // 2 + 1, sp - 1, sp, sp + 1))
+    assert C.rps(sp // 2) == 2 and widths[sp // 2].claim == (3, 1) and all(widths[w].claim[0] == widths[w].window_hw[0] for w in (sp // 2 + 1, sp - 1, sp, sp + 1))
+    # three poses on three different scenes, once with T = 16 and once with T = 1
+    for T in (16, 1):
+        assert any(len(c.taus) == T and len(c.depth_test) >= 3 and len(set(c.scene_index[:3].tolist())) == 3 and c.claim[0] >= 2 for c in C.STRIP_CASES)
+    assert C.MULTI_STRIP_CASE in by and by[C.MULTI_STRIP_CASE].claim[0] == 3
+    assert not set(C.STRIP_NAMES) & set(NAMES)  # nothing here goes through the rasteriser of the chain tests
+
+
+def test_window_strip_case_is_what_it_says():
+    c = C.strip_case(C.WINDOW_STRIP_CASE)
+    counts, _, refs = C.strip_expected(C.WINDOW_STRIP_CASE)
+    (h, w), (H, W) = c.window_hw, c.frame_hw
+    n_strips, last = c.claim
+    r0 = (n_strips - 1) * C.rps(w)
+    assert n_strips >= 2 and W % 4 != 0 and C.rps(W) != C.rps(w)
+    assert [c.refused(b) for b in range(6)] == [False, False, True, False, True, False]
+    x0, y0 = c.origin(2)
+    assert x0 + w > W and 0 <= c.scene_index[2] < len(c.depth_test)       # row 2: the window reaches outside the frame
+    assert c.scene_index[4] == len(c.depth_test) and not c._replace(scene_index=np.zeros(6, np.int32)).refused(4)  # row 4: the scene alone
+    valid = [0, 1, 3, 5]
+    assert len({c.origin(b)[0] % 4 for b in valid}) >= 3 and all(c.origin(b)[1] > 0 for b in valid)
+    assert all(c.origin(b)[1] + h < H for b in valid)  # the bottom side is the window's own in every row: cut_b holds
+    hit_rows = [np.nonzero(((c.depth_est[b] > 0) | (c.depth_gt[b] > 0)).any(1))[0] for b in range(6)]
+    assert hit_rows[0].min() == r0 and hit_rows[0].max() == h - 2                   # the last strip only, clear of the bottom side
+    assert hit_rows[1].tolist() == [r0 - 1, r0]                                    # the two rows where the strips meet
+    assert hit_rows[3].min() < r0 and hit_rows[3].max() == h - 1 and counts[3, 2] > 0   # cut by the bottom side: edge from the last strip
+    assert hit_rows[5].min() == 0 and hit_rows[5].max() >= r0 and counts[5, 2] > 0      # cut by the top side: edge from the first strip
+    assert counts[0, 2] == 0 and counts[1, 2] == 0 and counts[0, 0] > 0 and counts[1, 0] > 0
+    # the held rows score the same in a call without windows, where the frame has strips of its own
+    assert tuple(C.WINDOW_STRIP_HELD) == (0, 1)
+    full = C.full_frame_of(c, C.WINDOW_STRIP_HELD)
+    assert full.claim[0] >= 3 and full.claim != c.claim
+    fc, fe, _ = C.score_call(full)
+    assert np.array_equal(fc, counts[list(C.WINDOW_STRIP_HELD)])
+
+
+def test_probes_are_single_pixels_on_every_strip_edge():
+    for h, w in C.PROBE_SHAPES:
+        n_strips, _ = C.strips_of(h, w)
+        px = C.probe_pixels(h, w)
+        rows, cols = {y for y, _ in px}, {x for _, x in px}
+        assert n_strips >= 3 and cols == {0, w - 1} and h - 1 in rows
+        assert rows == {s * C.rps(w) for s in range(n_strips)} | {min(h, (s + 1) * C.rps(w)) - 1 for s in range(n_strips)}
+        calls = C.probe_calls(h, w)
+        assert sum(len(part) for _, part in calls) == len(px) and all(len(part) <= 6 for _, part in calls)
+        for c, part in calls:
+            counts, errors, _ = C.score_call(c)
+            assert all(int((c.depth_est[b] > 0).sum()) == 1 and c.depth_est[b, y, x] > 0 for b, (y, x) in enumerate(part))
+            assert np.array_equal(counts, np.tile(np.asarray([1, 1, 0, 0], np.int32), (len(part), 1))) and not errors.any()
+
+
+def test_tie_pixels_sit_on_their_thresholds():
+    """At each named pixel of the tie pose the two sides of the named comparison are the same fp64 bits, and the kernel's arithmetic there
+    is exact (dyadic depths, a ray length of 1, 3/2 or 3).  One fp32 step of the deciding depth to either side decides the pixel the two
+    ways.  Every OTHER decided comparison of the case keeps the margin."""
+    c = C.strip_case(C.TIE_CASE)
+    assert c.delta == 3 / 64 and c.taus[0] * float(c.diameter[0]) == 3 / 16 and float(np.float32(c.delta)) == c.delta
+    n = orc.ray_length(c.K[0], (17, 17))
+    thr = np.asarray(c.taus, np.float32).astype(np.float64) * 0.5
+    bits = lambda v: np.float64(v).view(np.int64)  # noqa: E731
+    P = [orc.pixels(c.depth_est[b], c.depth_gt[b], c.depth_test[0], n, c.delta, thr) for b in range(4)]
+    at, up, down = (P[b] for b in C.TIE_POSES)
+    named = {kind: np.zeros((17, 17), dtype=bool) for kind in ("gt", "est", "cost")}
+    assert len({(y, x) for y, x, _ in C.TIE_PIXELS}) == len(C.TIE_PIXELS) == 13 and {k for _, _, k in C.TIE_PIXELS} == set(named)
+    for y, x, kind in C.TIE_PIXELS:
+        assert n[y, x] == {0: 1.0, 20: 1.5, 128: 3.0}[(y - 8) ** 2 + (x - 8) ** 2]
+        named[kind][y, x] = True
+        lhs = {"gt": "lhs_gt", "est": "lhs_est", "cost": "lhs_cost"}[kind]
+        rhs = c.delta if kind != "cost" else thr[0]
+        assert bits(getattr(at, lhs)[y, x]) == bits(rhs), (y, x, kind)
+        assert getattr(up, lhs)[y, x] > rhs > getattr(down, lhs)[y, x]
+        if kind == "gt":    # <= delta holds on the tie
+            assert at.vis_gt[y, x] and down.vis_gt[y, x] and not up.vis_gt[y, x] and at.margin_gt[y, x] == 0
+        elif kind == "est":
+            assert at.vis_est[y, x] and down.vis_est[y, x] and not up.vis_est[y, x] and not at.vis_gt[y, x] and at.margin_est[y, x] == 0
+        else:               # >= tau d holds on the tie
+            assert at.costly[0, y, x] and up.costly[0, y, x] and not down.costly[0, y, x] and at.margin_cost[0, y, x] == 0
+    # every comparison of the case but the 13 named ones of the tie pose
+    for b, p in enumerate(P):
+        free = b != C.TIE_POSES[0]
+        m = min(np.where(named["gt"] & ~free, np.inf, p.margin_gt).min(), np.where(named["est"] & ~free, np.inf, p.margin_est).min(),
+                np.where(named["cost"] & ~free, np.inf, p.margin_cost[0]).min(), p.margin_cost[1:].min())
+        print(f"{C.TIE_CASE} pose {b}: the least margin off the named ties {m:.3g}")
+        assert m >= C.MARGIN
+    assert C.strip_expected(C.TIE_CASE)[2][0].margin == 0  # and `score` reports the ties
+
+
+def test_value_pose_holds_every_value_that_is_not_a_hit():
+    """-1, -0.0 and NaN in est, gt and the scene: no hit, or no measurement -- each where reading it as a depth would change a count."""
+    c = C.strip_case(C.TIE_CASE)
+    b = C.VALUE_POSE
+    ref = C.strip_expected(C.TIE_CASE)[2][b]
+    assert np.isnan(c.depth_est[b]).any() and np.isnan(c.depth_gt[b]).any() and np.isnan(c.depth_test).any()
+    assert (np.signbit(c.depth_est[b]) & (c.depth_est[b] == 0)).any() and (np.signbit(c.depth_test) & (c.depth_test == 0)).any()
+    assert (c.depth_est[b] == -1).any() and (c.depth_gt[b] == -1).any() and (c.depth_test == -1).any()
+    want_g, want_e = np.zeros((17, 17), dtype=bool), np.zeros((17, 17), dtype=bool)
+    for y, x, e, g, t in C.VALUE_PIXELS:  # the header by hand: a depth of 1 hits, None does not; the scene at 1 hides nothing, None is missing
+        want_g[y, x:x + 3], want_e[y, x:x + 3] = g == 1.0, e == 1.0
+    assert np.array_equal(ref.vis_gt, want_g) and np.array_equal(ref.vis_est, want_e)
+    assert ref.counts.tolist() == [15, 3, 0, 0, 0] and ref.margin >= C.MARGIN
+
+
+@pytest.mark.parametrize("name", C.STRIP_NAMES + tuple(NAMES))
+def test_launch_restatement_is_the_oracle(name):
+    c = C.strip_case(name) if name in C.STRIP_NAMES else C.as_call(name)
+    want = C.strip_expected(name)[0] if name in C.STRIP_NAMES else C.expected(name)[0]
+    assert np.array_equal(launch_counts(c), want)
+    if name == C.WINDOW_STRIP_CASE:
+        full = C.full_frame_of(c, C.WINDOW_STRIP_HELD)
+        assert np.array_equal(launch_counts(full), want[list(C.WINDOW_STRIP_HELD)])
+
+
+def test_launch_restatement_counts_the_probes():
+    for c in _probe_cases():
+        assert np.array_equal(launch_counts(c), C.score_call(c)[0])
+
+
+def test_planted_mistakes_are_caught_by_the_new_cases_and_not_by_the_old():
+    """The table of the gap: every mistake changes a count of the case named for it, and (but for the one that any batch of two poses
+    shows) changes nothing on CASES, whose maps are all one strip and whose comparisons all keep the margin."""
+    new = [C.strip_case(n) for n in C.STRIP_NAMES]
+    old = [C.as_call(n) for n in NAMES]
+    right = {c.name: launch_counts(c) for c in new + old}
+    for mistake, named in MISTAKES.items():
+        caught_by = [c.name for c in new if not np.array_equal(launch_counts(c, mistake), right[c.name])]
+        seen_before = [c.name for c in old if not np.array_equal(launch_counts(c, mistake), right[c.name])]
+        print(f"{mistake}: caught by {caught_by}; by CASES: {seen_before}")
+        assert named in caught_by, (mistake, caught_by)
+        assert bool(seen_before) == (mistake in SEEN_AT_ONE_STRIP), (mistake, seen_before)
+    # every case of two strips or more catches the two mistakes that any later strip shows
+    for c in new:
+        if c.claim[0] >= 2:
+            for mistake in ("last_row_dropped", "scene_row_local"):
+                assert not np.array_equal(launch_counts(c, mistake), right[c.name]), (c.name, mistake)
+    # a probe on a strip's last row is lost with that row; one in a later strip moves with the scene's row only where the scene differs
+    lost = sum(int((launch_counts(c, "last_row_dropped")[:, 0] == 0).sum()) for c in _probe_cases())
+    assert lost >= 3 * len(C.PROBE_SHAPES)

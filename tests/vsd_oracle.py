@@ -11,6 +11,10 @@ One pose per call.  depth_est / depth_gt are (h,w), depth_test the whole (H,W) f
               every pixel of the intersection.  The kernel's square root and division may differ from numpy's in the last fp64 bits; a case
               must keep 2^-30 clear (tests/test_vsd_oracle.py), so that no such difference can decide a pixel.  1.0 where nothing is compared.
     vis_gt, vis_est    the masks, for the tests that reason about single pixels
+
+`pixels` is steps 2 to 4 on maps of any one shape, with each comparison's left side and its margin pixel by pixel (0: a tie) and the three
+predicates `<= delta`, `>= tau d` and `d > 0` as arguments: `score` is built on it, tests/test_vsd_oracle.py restates the kernel's launch
+shape with it, strip by strip, and plants its mistakes through it.
 """
 from __future__ import annotations
 
@@ -56,6 +60,64 @@ def _rel(lhs, rhs):
     return np.abs(lhs - rhs) / np.maximum(np.abs(rhs), TINY)
 
 
+class Pixels(NamedTuple):
+    """Steps 2 to 4 pixel by pixel, for the tests that restate the kernel's launch shape or plant a mistake in a comparison."""
+    hit: np.ndarray      # est or gt hits: the pixels that edge counts on a cut side
+    vis_gt: np.ndarray
+    vis_est: np.ndarray
+    costly: np.ndarray   # (T,) + shape: the cost predicates, inside the intersection only
+    lhs_gt: np.ndarray   # dist_gt - dist_test, dist_est - dist_test and |dist_gt - dist_est|: the left sides of the three comparisons
+    lhs_est: np.ndarray
+    lhs_cost: np.ndarray
+    margin_gt: np.ndarray    # the relative distance of each DECIDED comparison to its threshold, inf where it is not consulted: 0 is a tie
+    margin_est: np.ndarray
+    margin_cost: np.ndarray  # (T,) + shape
+
+
+def pixels(de32, dg32, dt32, n, delta, thr, dist_dtype=np.float64, le=np.less_equal, ge=np.greater_equal, hit=lambda d: d > 0) -> Pixels:
+    """Steps 2 to 4 on float32 maps of one shape (dt32: the scene's depth under the window) with the ray lengths `n`; delta and thr
+    (= tau_k d) are fp64 values of fp32 numbers.  `le`, `ge` and `hit` are the contract's `<= delta`, `>= tau_k d` and `d > 0`: a test
+    passes another to state a mistake."""
+    with np.errstate(invalid="ignore"):
+        he, hg, missing = hit(de32), hit(dg32), ~(dt32 > 0)
+        dist_e = (de32.astype(np.float64) * n).astype(dist_dtype).astype(np.float64)
+        dist_g = (dg32.astype(np.float64) * n).astype(dist_dtype).astype(np.float64)
+        dist_t = (dt32.astype(np.float64) * n).astype(dist_dtype).astype(np.float64)
+        over_g = dist_g - dist_t
+        over_e = dist_e - dist_t
+        vis_g = hg & (missing | le(over_g, delta))
+        vis_e = he & (missing | le(over_e, delta) | vis_g)
+        inter = vis_g & vis_e
+        diff = np.abs(dist_g - dist_e)
+        costly = np.stack([inter & ge(diff, t) for t in thr])
+        # (the kernel evaluates est's comparison whether or not vis_gt then settles the pixel)
+        m_g = np.where(hg & ~missing, _rel(over_g, delta), np.inf)
+        m_e = np.where(he & ~missing, _rel(over_e, delta), np.inf)
+        m_c = np.stack([np.where(inter, _rel(diff, t), np.inf) for t in thr])
+    return Pixels(he | hg, vis_g, vis_e, costly, over_g, over_e, diff, m_g, m_e, m_c)
+
+
+def cut_sides(hw, frame_hw, window_xy=(0, 0)):
+    """The pixels of the window's border on a side that is not the frame's own: where a hit counts as edge."""
+    (h, w), (H, W), (x0, y0) = hw, frame_hw, window_xy
+    border = np.zeros((h, w), dtype=bool)
+    if x0 > 0:
+        border[:, 0] = True
+    if x0 + w < W:
+        border[:, -1] = True
+    if y0 > 0:
+        border[0, :] = True
+    if y0 + h < H:
+        border[-1, :] = True
+    return border
+
+
+def errors_of(counts):
+    """Step 5: (T,) float32 from one pose's (T+3,) counts."""
+    nu, ni = int(counts[0]), int(counts[1])
+    return np.asarray([1.0 if nu == 0 else np.float64(int(c) + nu - ni) / np.float64(nu) for c in counts[3:]], dtype=np.float64).astype(np.float32)
+
+
 def score(depth_est, depth_gt, depth_test, K, delta, taus, diameter=None, window_xy=(0, 0), pixel_center=(0.0, 0.0), dist_dtype=np.float64) -> Ref:
     """dist_dtype=np.float32 rounds the three distance images to fp32 before they are subtracted, as BOP's Python does (the first of the
     two deliberate differences of include/lc_amd_vsd.h): `flipped_pixels` counts the pixels that this decides."""
@@ -69,43 +131,12 @@ def score(depth_est, depth_gt, depth_test, K, delta, taus, diameter=None, window
     taus = np.asarray(taus, dtype=np.float32).astype(np.float64)
     diam = 1.0 if diameter is None else float(np.float32(diameter))
     n = ray_length(K, (h, w), (x0, y0), pixel_center)
-    with np.errstate(invalid="ignore"):
-        he, hg, missing = de32 > 0, dg32 > 0, ~(dt32 > 0)
-        dist_e = (de32.astype(np.float64) * n).astype(dist_dtype).astype(np.float64)
-        dist_g = (dg32.astype(np.float64) * n).astype(dist_dtype).astype(np.float64)
-        dist_t = (dt32.astype(np.float64) * n).astype(dist_dtype).astype(np.float64)
-        over_g = dist_g - dist_t
-        over_e = dist_e - dist_t
-        vis_g = hg & (missing | (over_g <= delta))
-        vis_e = he & (missing | (over_e <= delta) | vis_g)
-    union, inter = vis_g | vis_e, vis_g & vis_e
-    diff = np.abs(dist_g - dist_e)
-    thr = taus * diam
-    costly = [inter & (diff >= t) for t in thr]
-    cost = [m.sum() for m in costly]
-    border = np.zeros((h, w), dtype=bool)
-    if x0 > 0:
-        border[:, 0] = True
-    if x0 + w < W:
-        border[:, -1] = True
-    if y0 > 0:
-        border[0, :] = True
-    if y0 + h < H:
-        border[-1, :] = True
-    edge = (border & (he | hg)).sum()
-    counts = np.asarray([union.sum(), inter.sum(), edge, *cost], dtype=np.int32)
-    nu, ni = int(counts[0]), int(counts[1])
-    errors = np.asarray([1.0 if nu == 0 else np.float64(int(c) + nu - ni) / np.float64(nu) for c in counts[3:]], dtype=np.float64).astype(np.float32)
-    margins = [1.0]
-    consulted_g = hg & ~missing
-    consulted_e = he & ~missing  # (the kernel evaluates it whether or not vis_gt then settles the pixel)
-    if consulted_g.any():
-        margins.append(float(_rel(over_g[consulted_g], delta).min()))
-    if consulted_e.any():
-        margins.append(float(_rel(over_e[consulted_e], delta).min()))
-    if inter.any():
-        margins.append(float(min(_rel(diff[inter], t).min() for t in thr)))
-    return Ref(counts, errors, min(margins), vis_g, vis_e, np.stack([vis_g, vis_e, *costly], -1))
+    p = pixels(de32, dg32, dt32, n, delta, taus * diam, dist_dtype)
+    union, inter = p.vis_gt | p.vis_est, p.vis_gt & p.vis_est
+    edge = (cut_sides((h, w), (H, W), (x0, y0)) & p.hit).sum()
+    counts = np.asarray([union.sum(), inter.sum(), edge, *(m.sum() for m in p.costly)], dtype=np.int32)
+    margin = min(1.0, float(p.margin_gt.min()), float(p.margin_est.min()), float(p.margin_cost.min()))
+    return Ref(counts, errors_of(counts), margin, p.vis_gt, p.vis_est, np.stack([p.vis_gt, p.vis_est, *p.costly], -1))
 
 
 def flipped_pixels(*args, **kw) -> int:
