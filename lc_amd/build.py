@@ -13,17 +13,15 @@
     maskcrop lc_amd/_C/liblc_amd_maskcrop.so lc_amd/csrc/maskcrop/    include/lc_amd_maskcrop.h the training mask crops: warps, valid count, check points
     augment  lc_amd/_C/liblc_amd_augment.so  lc_amd/csrc/augment/     include/lc_amd_augment.h  the training crops' background switch and colour augmentation
     rle      lc_amd/_C/liblc_amd_rle.so      lc_amd/csrc/rle/         include/lc_amd_rle.h      the store of COCO run-length masks: index, decode, encode
-    geometry lc_amd/_C/liblc_amd_geometry.so lc_amd/csrc/geometry/    include/lc_amd_geometry.h the training crops' geometry drawn from the seed word (LATE_TARGETS)
+    geometry lc_amd/_C/liblc_amd_geometry.so lc_amd/csrc/geometry/    include/lc_amd_geometry.h the training crops' geometry drawn from the seed word
 
 A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`): code that
 two libraries need exists once there (lc_shared.h: main, posecov, models, symerr; lc_warp_grid.h: crop, maskcrop; lc_ray_length.h: vsd,
-gtinfo; lc_wave_int.h: vsd, gtinfo, maskcrop), and no side library restates another's arithmetic -- but for the five lines of the
-integer hash finaliser of the device's random numbers that augment has in common with maskcrop, and the wave scans that rle writes out
-for itself (tests/test_posecov_host.py states each shared header's users); geometry restates the same five lines once more.
-There are two tuples.  `TARGETS` is the twelve libraries above geometry, in build order: the tests of each of them state its place in
-that tuple and the tuple's length, so it is closed.  A library that comes after them goes into `LATE_TARGETS`, and `ALL_TARGETS =
-TARGETS + LATE_TARGETS` is every library in build order: whoever builds, packages, hashes or compares "all of them" iterates
-`ALL_TARGETS`, the twelve first.  Every function takes the library it works on as a `Target` (default: the hot-path library)."""
+gtinfo; lc_wave_int.h: vsd, gtinfo, maskcrop; lc_keyed_hash.h: maskcrop, augment, geometry; lc_byte_finish.h: crop, augment), and no side
+library restates another's arithmetic -- but for the wave scans that rle writes out for itself.  `TARGETS` is every library in build
+order: whoever builds, packages, hashes or compares "all of them" iterates it, and tests/test_libraries_host.py states it row by row
+(each library's files, marker, shared headers and includes, and each shared header's users).  Every function takes the library it
+works on as a `Target` (default: the hot-path library)."""
 from __future__ import annotations
 
 import glob
@@ -63,6 +61,8 @@ SHARED_H = os.path.join(SHARED, "lc_shared.h")  # the fp64 cross-lane layer: the
 WARP_GRID_H = os.path.join(SHARED, "lc_warp_grid.h")  # the fixed-point warp coordinates and launch geometry of CROP and MASKCROP
 RAY_LENGTH_H = os.path.join(SHARED, "lc_ray_length.h")  # the ray length through a pixel and the phase-aligned group loads of VSD and GTINFO
 WAVE_INT_H = os.path.join(SHARED, "lc_wave_int.h")  # the integer wave butterflies of VSD, GTINFO and MASKCROP
+KEYED_HASH_H = os.path.join(SHARED, "lc_keyed_hash.h")  # the keyed integer hash of the device's random numbers of MASKCROP, AUGMENT and GEOMETRY
+BYTE_FINISH_H = os.path.join(SHARED, "lc_byte_finish.h")  # the finished output value of an image byte of CROP and AUGMENT
 
 
 def _side(name: str, shared: tuple = ()) -> Target:
@@ -75,7 +75,7 @@ MAIN = Target("main", CSRC, "lc_amd.h", SO_PATH, b"LC_AMD_SRC_HASH:", (SHARED_H,
 OPTIM = _side("optim")  # the fused optimizer step (lc_amd.optim)
 POSECOV = _side("posecov", (SHARED_H,))  # the test-time pose covariance (lc_amd.posecov)
 RENDER = _side("render")  # the depth rasteriser (lc_amd.render)
-CROP = _side("crop", (WARP_GRID_H,))  # the zoom-in crops (lc_amd.crops)
+CROP = _side("crop", (BYTE_FINISH_H, WARP_GRID_H))  # the zoom-in crops (lc_amd.crops)
 MODELS = _side("models", (SHARED_H,))  # the offline model preparation (lc_amd.models, python -m lc_amd.prep_models); loaded by no training or test-time path
 # the symmetry-aware evaluation errors (lc_amd.metrics.compute_sym_pose_errors): its table rules are those of the label kernels, stated once in lc_sym_args.h
 SYMERR = _side("symerr", (SHARED_H, os.path.join(CSRC, "lc_sym_args.h")))
@@ -83,18 +83,13 @@ VSD = _side("vsd", (RAY_LENGTH_H, WAVE_INT_H))  # the evaluation error that read
 # the dataset annotations: visibility records, composed scene depth (lc_amd.gtinfo, python -m lc_amd.gen_gt_info); shares the ray length with VSD
 GTINFO = _side("gtinfo", (RAY_LENGTH_H, WAVE_INT_H))
 # the training loader's per-instance mask crops (lc_amd.maskcrop); shares the coordinates with CROP
-MASKCROP = _side("maskcrop", (WARP_GRID_H, WAVE_INT_H))
-# the training loader's background switch and colour augmentation (lc_amd.augment); includes no shared header: its device code writes out
-# the same five-line integer hash finaliser as maskcrop's (the per-pixel random numbers; nothing to do with source_hash)
-AUGMENT = _side("augment")
+MASKCROP = _side("maskcrop", (KEYED_HASH_H, WARP_GRID_H, WAVE_INT_H))
+# the training loader's background switch and colour augmentation (lc_amd.augment); finishes a byte as CROP does, hashes as MASKCROP does
+AUGMENT = _side("augment", (BYTE_FINISH_H, KEYED_HASH_H))
 RLE = _side("rle")  # the training loader's device-resident store of run-length masks (lc_amd.rle); includes no shared header
-# the training loader's geometry drawn on the device from the seed word (lc_amd.geometry); includes no shared header: the five-line finaliser again
-GEOMETRY = _side("geometry")
-# the twelve whose places their own tests state: closed (see the docstring)
-TARGETS = (MAIN, OPTIM, POSECOV, RENDER, CROP, MODELS, SYMERR, VSD, GTINFO, MASKCROP, AUGMENT, RLE)
-LATE_TARGETS = (GEOMETRY,)  # the libraries after them
-# every library, in build order: whoever builds, hashes or compares "all of them" iterates this
-ALL_TARGETS = TARGETS + LATE_TARGETS
+GEOMETRY = _side("geometry", (KEYED_HASH_H,))  # the training loader's geometry drawn on the device from the seed word (lc_amd.geometry)
+# every library, in build order
+TARGETS = (MAIN, OPTIM, POSECOV, RENDER, CROP, MODELS, SYMERR, VSD, GTINFO, MASKCROP, AUGMENT, RLE, GEOMETRY)
 HASH_MARKER = MAIN.hash_marker
 
 
@@ -249,5 +244,5 @@ def build_variant(name: str, flags, verbose: bool = False) -> str:
 
 
 if __name__ == "__main__":
-    for t in ALL_TARGETS:
+    for t in TARGETS:
         print(build(force=True, verbose=True, target=t))

@@ -20,8 +20,7 @@
 // Global loads and stores move four pixels (4 bytes of uint8, 16 of the mask and of an fp32 output) where w is a multiple of four and
 // the pointers are aligned to it; element by element otherwise.
 //
-// The hash is maskcrop's (MurmurHash3's finaliser, include/lc_amd_maskcrop.h), restated here: the headers of csrc/shared/ are pinned to
-// the libraries that include them.
+// The hash is maskcrop's (include/lc_amd_maskcrop.h): shared/lc_keyed_hash.h.
 //
 // Bounds: every quad is judged against the image before it is loaded or stored, the background index and the NULL inputs are judged
 // before they are used, and a refused row reads its crop only.
@@ -31,6 +30,8 @@
 #include <string>
 
 #include "../../../include/lc_amd_augment.h"
+#include "../shared/lc_byte_finish.h"
+#include "../shared/lc_keyed_hash.h"
 
 #ifndef LC_AMD_AUGMENT_SRC_HASH
 #define LC_AMD_AUGMENT_SRC_HASH "unrecorded"
@@ -79,45 +80,8 @@ struct Params {
     unsigned char* lut_out;          // (B,3,256) or null
 };
 
-template <int DT> struct Store { using type = unsigned short; };
-template <> struct Store<LC_AUGMENT_U8> { using type = unsigned char; };
-template <> struct Store<LC_AUGMENT_F32> { using type = float; };
-
-template <typename T> struct alignas(4 * sizeof(T)) Vec4 { T v[4]; };
-
-// The finished output value of byte v in channel c (lc_amd_crop.h): v / 255, then (. - mean) / std, each an IEEE fp32 operation; a 16-bit
-// type is rounded once (nearest even) from that fp32.
-template <int DT>
-__device__ inline typename Store<DT>::type finish(int v, int c, const Params& p) {
-    if constexpr (DT == LC_AUGMENT_U8) {
-        return (unsigned char)v;
-    } else {
-        float q = __fdiv_rn((float)v, 255.0f);
-        if (p.normalize) {
-            q = __fsub_rn(q, p.mean[c]);
-            q = __fdiv_rn(q, p.std[c]);
-        }
-        if constexpr (DT == LC_AUGMENT_F32) {
-            return q;
-        } else if constexpr (DT == LC_AUGMENT_F16) {
-            return __builtin_bit_cast(unsigned short, (_Float16)q);
-        } else {
-            const unsigned u = __float_as_uint(q);
-            if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)0x7fc0;
-            return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-        }
-    }
-}
-
-// MurmurHash3's 32-bit finaliser
-__device__ __forceinline__ unsigned fmix32(unsigned v) {
-    v ^= v >> 16;
-    v *= 0x85ebca6bu;
-    v ^= v >> 13;
-    v *= 0xc2b2ae35u;
-    v ^= v >> 16;
-    return v;
-}
+// the finished output value of a byte (lc_amd_crop.h): shared/lc_byte_finish.h, with the zoom-in crops
+static_assert(LC_AUGMENT_U8 == kByteU8 && LC_AUGMENT_F32 == kByteF32 && LC_AUGMENT_F16 == kByteF16 && LC_AUGMENT_BF16 == kByteBF16, "the dtype codes of lc_byte_finish.h");
 
 // What a workgroup knows of its row once it is judged
 struct Row {
@@ -256,9 +220,7 @@ __device__ __forceinline__ unsigned row_key(const Params& p, int b) {
         const unsigned long long s = *p.seed;
         lo = (unsigned)s, hi = (unsigned)(s >> 32);
     }
-    unsigned k = fmix32(lo);
-    k = fmix32(k ^ hi);
-    return fmix32(k ^ (unsigned)(p.sample_id ? p.sample_id[b] : b));
+    return sample_state(seed_state(lo, hi), (unsigned)(p.sample_id ? p.sample_id[b] : b));
 }
 
 // exp(x) for x <= 0: x = k ln 2 + r with |r| <= ln 2 / 2 and the rational form of fdlibm's e_exp.c on r (below one unit in the last
@@ -324,7 +286,7 @@ __device__ __forceinline__ void draw_row(const Params& p, int b, bool store, int
     const lc_augment_draw_config& cfg = p.cfg;
     const unsigned k = row_key(p, b);
     const auto key = [k](unsigned op, unsigned i) { return fmix32(fmix32(k ^ op) ^ i); };
-    const auto u = [&key](unsigned op, unsigned i) { return (double)(key(op, i) >> 8) * 0x1p-24; };  // exact
+    const auto u = [&key](unsigned op, unsigned i) { return key_uniform(key(op, i)); };
     // one value per channel where the op's own draw says so, else the first for all three
     const auto per_channel = [&u](unsigned op, double prob, int c) { return u(op, 1) < prob ? u(op, 2 + c) : u(op, 2); };
 

@@ -21,6 +21,7 @@
 #include <string>
 
 #include "../../../include/lc_amd_crop.h"
+#include "../shared/lc_byte_finish.h"
 #include "../shared/lc_warp_grid.h"
 
 #ifndef LC_AMD_CROP_SRC_HASH
@@ -53,35 +54,10 @@ struct Params {
     float mean[3], std[3];
 };
 
-template <int DT> struct Store { using type = unsigned short; };
-template <> struct Store<LC_CROP_U8> { using type = unsigned char; };
-template <> struct Store<LC_CROP_F32> { using type = float; };
-
-template <typename T> struct alignas(4 * sizeof(T)) Vec4 { T v[4]; };
-
-// The finished output value of byte v in channel c: v / 255, then (. - mean) / std, each an IEEE fp32 operation; a 16-bit type is
-// rounded once (nearest even) from that fp32.
-template <int DT>
-__device__ inline typename Store<DT>::type finish(int v, int c, const Params& p) {
-    if constexpr (DT == LC_CROP_U8) {
-        return (unsigned char)v;
-    } else {
-        float q = __fdiv_rn((float)v, 255.0f);
-        if (p.normalize) {
-            q = __fsub_rn(q, p.mean[c]);
-            q = __fdiv_rn(q, p.std[c]);
-        }
-        if constexpr (DT == LC_CROP_F32) {
-            return q;
-        } else if constexpr (DT == LC_CROP_F16) {
-            return __builtin_bit_cast(unsigned short, (_Float16)q);
-        } else {
-            const unsigned u = __float_as_uint(q);
-            if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)0x7fc0;
-            return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-        }
-    }
-}
+using lc::Store;
+using lc::Vec4;
+using lc::finish;  // the finished output value of a byte: shared/lc_byte_finish.h, with the colour augmentation
+static_assert(LC_CROP_U8 == lc::kByteU8 && LC_CROP_F32 == lc::kByteF32 && LC_CROP_F16 == lc::kByteF16 && LC_CROP_BF16 == lc::kByteBF16, "the dtype codes of lc_byte_finish.h");
 
 template <int DT, int C, bool LINEAR>
 __global__ __launch_bounds__(kThreads) void lc_crop_warp_kernel(const Params p) {

@@ -11,8 +11,7 @@
 // rounds each Horner step twice.  The cosine and the sine are the definition's polynomial on its exactly reduced argument, never a
 // library call.  Outputs are plain stores.
 //
-// The hash is maskcrop's and augment's (MurmurHash3's finaliser), restated here: the headers of csrc/shared/ are pinned to the libraries
-// that include them.
+// The hash is maskcrop's and augment's: shared/lc_keyed_hash.h.
 //
 // Bounds: thread b >= B returns before it reads; row b reads sample_id[b], bbox[4 b .. 4 b + 3], cam_K[b K_stride .. + 8] (K_stride 0 or
 // 9, checked on the host) and bg_hw[2 b .. 2 b + 1], and writes its own rows of the outputs; no input VALUE forms an address.
@@ -23,6 +22,7 @@
 #include <string>
 
 #include "../../../include/lc_amd_geometry.h"
+#include "../shared/lc_keyed_hash.h"
 
 #ifndef LC_AMD_GEOMETRY_SRC_HASH
 #define LC_AMD_GEOMETRY_SRC_HASH "unrecorded"
@@ -41,25 +41,12 @@ int fail(int code, std::string msg) {
 
 constexpr int kThreads = 64;
 
-// MurmurHash3's 32-bit finaliser
-__device__ __forceinline__ unsigned fmix32(unsigned v) {
-    v ^= v >> 16;
-    v *= 0x85ebca6bu;
-    v ^= v >> 13;
-    v *= 0xc2b2ae35u;
-    v ^= v >> 16;
-    return v;
-}
-
 // The key state of (seed, sample_id, op): key(op, i) = fmix32(state ^ i)
 __device__ inline unsigned key_state(unsigned long long seed, int sample_id, unsigned op) {
-    unsigned k = fmix32((unsigned)(seed & 0xffffffffull));
-    k = fmix32(k ^ (unsigned)(seed >> 32));
-    k = fmix32(k ^ (unsigned)sample_id);
-    return fmix32(k ^ op);
+    return fmix32(sample_state(seed_state((unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32)), (unsigned)sample_id) ^ op);
 }
 
-__device__ inline double uniform(unsigned state, unsigned i) { return __dmul_rn((double)(fmix32(state ^ i) >> 8), 0x1p-24); }  // exact
+__device__ inline double uniform(unsigned state, unsigned i) { return key_uniform(fmix32(state ^ i)); }
 
 // fl(pi / 4) and (-1)^(k/2) / k! rounded to fp64, k = 3, 5, ..., 17 and k = 2, 4, ..., 16: PI_4, SIN_C and COS_C of lc_amd/geometry.py
 constexpr double kPi4 = 0x1.921fb54442d18p-1;

@@ -26,6 +26,7 @@
 #include <string>
 
 #include "../../../include/lc_amd_maskcrop.h"
+#include "../shared/lc_keyed_hash.h"
 #include "../shared/lc_warp_grid.h"
 #include "../shared/lc_wave_int.h"
 
@@ -175,16 +176,6 @@ __global__ __launch_bounds__(kThreads) void lc_mask_warp_kernel(const Params p) 
     }
 }
 
-// MurmurHash3's 32-bit finaliser
-__device__ __forceinline__ unsigned fmix32(unsigned v) {
-    v ^= v >> 16;
-    v *= 0x85ebca6bu;
-    v ^= v >> 13;
-    v *= 0xc2b2ae35u;
-    v ^= v >> 16;
-    return v;
-}
-
 // (key << 16) | p of pixel p under the round's state
 __device__ __forceinline__ unsigned long long composite(unsigned round_state, unsigned q) {
     return ((unsigned long long)fmix32(round_state ^ q) << 16) | q;
@@ -217,9 +208,7 @@ __global__ __launch_bounds__(kCkThreads) void lc_mask_check_kernel(const Params 
         return;
     }
     const unsigned char* noc = p.noc + (size_t)b * hw;
-    unsigned k = fmix32(p.seed_lo);
-    k = fmix32(k ^ p.seed_hi);
-    k = fmix32(k ^ (unsigned)(p.sample_id ? p.sample_id[b] : b));
+    const unsigned k = sample_state(seed_state(p.seed_lo, p.seed_hi), (unsigned)(p.sample_id ? p.sample_id[b] : b));
     if (tid == 0) s_n = 0;
     __syncthreads();
 

@@ -19,7 +19,7 @@
 //
 // Bounds: offsets, sizes, indices and origins are judged before they are used, every index into `ends` lies in [base, base + n) of a
 // judged mask, every byte of a window is addressed from in-window coordinates, and every write to counts_out is checked against cap.
-// The few lines of wave arithmetic are restated here: the headers of csrc/shared/ are pinned to the libraries that include them.
+// The few lines of wave arithmetic are written out here: the scans are 64-bit and paired, other types than shared/lc_wave_int.h folds.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

@@ -192,25 +192,11 @@ def test_gate_frequencies_over_4096_samples():
 def test_build_group_header_exports_and_source_hash():
     from lc_amd import augment, build
 
-    T = build.AUGMENT
-    others = [t for t in build.TARGETS if t is not T]
-    assert build.TARGETS[10] is T and len(others) == 11
-    assert build.TARGETS[:10] == (build.MAIN, build.OPTIM, build.POSECOV, build.RENDER, build.CROP, build.MODELS, build.SYMERR, build.VSD, build.GTINFO, build.MASKCROP)
-    assert T.so_path.endswith(os.path.join("_C", "liblc_amd_augment.so")) and T.header == "lc_amd_augment.h" and T.shared == ()
+    T = build.AUGMENT  # (its place among the libraries, its files and includes: tests/test_libraries_host.py)
     lib = augment.load()
     assert not build.is_stale(T)
     assert lib.lc_amd_augment_source_hash().decode() == build.source_hash(T) == build.embedded_hash(T.so_path, T.hash_marker)
     assert build.sources(T) == [os.path.join(build.CSRC, "augment", "lc_augment.hip")]
-
-    def mine(d):
-        return os.sep + "augment" + os.sep in d or d.endswith("lc_amd_augment.h")
-
-    for t in others:  # no other library sees this directory or header
-        assert not any(mine(d) for d in build._deps(t)), t.name
-    assert all(mine(d) for d in build._deps(T))
-    assert set(re.findall(r'#include "([^"]+)"', open(build.sources(T)[0]).read())) == {"../../../include/lc_amd_augment.h"}
-    doc = build.__doc__
-    assert "liblc_amd_augment.so" in doc and "lc_amd/csrc/augment/" in doc and "include/lc_amd_augment.h" in doc
 
     header = open(os.path.join(ROOT, "include", "lc_amd_augment.h")).read()
     text = re.sub(r"/\*.*?\*/", "", header, flags=re.S)

@@ -113,22 +113,8 @@ def test_embedded_source_hash_and_separate_sources():
     assert not build.is_stale(build.CROP)
     assert lib.lc_amd_crop_source_hash().decode() == build.source_hash(build.CROP) == build.embedded_hash(build.CROP.so_path, build.CROP.hash_marker)
     assert build.sources(build.CROP) == [os.path.join(build.CSRC, "crop", "lc_crop.hip")]
-    assert build.TARGETS[:5] == (build.MAIN, build.OPTIM, build.POSECOV, build.RENDER, build.CROP)
-    others = [t for t in build.TARGETS if t is not build.CROP]
-    assert len(others) == 11
-
-    def mine(s):  # (maskcrop's own directory and files carry the word inside another)
-        return os.path.basename(s).startswith(("lc_crop", "lc_amd_crop")) or os.sep + "crop" + os.sep in s
-
-    for t in others:  # no other library sees this directory or header
-        assert not any(mine(s) for s in build._deps(t)), t.name
-    assert all(mine(s) or s == build.WARP_GRID_H for s in build._deps(build.CROP))
-    for t in build.TARGETS[:4]:  # the statement as it stood for the libraries before this one: not even the word in a file's name
-        assert not any("crop" in os.path.basename(s) for s in build._deps(t)), t.name
-    assert len({build.source_hash(t) for t in build.TARGETS}) == 12
-    src = open(build.sources(build.CROP)[0]).read()
-    assert re.findall(r'#include "([^"]+)"', src) == ["../../../include/lc_amd_crop.h", "../shared/lc_warp_grid.h"]
-    assert build.CROP.shared == (build.WARP_GRID_H,)
+    for t in (build.MAIN, build.OPTIM, build.POSECOV, build.RENDER):  # the libraries before this one: not even the word in a file's name
+        assert not any("crop" in os.path.basename(s) for s in build._deps(t)), t.name  # (its directory and header: tests/test_libraries_host.py)
 
 
 def _call(lib, **over):

@@ -150,25 +150,11 @@ def test_batch_contract_of_the_oracle():
 def test_build_group_header_exports_and_source_hash():
     from lc_amd import build, maskcrop
 
-    T = build.MASKCROP
-    others = [t for t in build.TARGETS if t is not T]
-    assert build.TARGETS.index(T) == 9 and len(others) == 11  # tenth, after the nine before it
-    assert T.so_path.endswith(os.path.join("_C", "liblc_amd_maskcrop.so")) and T.header == "lc_amd_maskcrop.h" and T.shared == (build.WARP_GRID_H, build.WAVE_INT_H)
+    T = build.MASKCROP  # (its place among the libraries, its files and includes: tests/test_libraries_host.py)
     lib = maskcrop.load()
     assert not build.is_stale(T)
     assert lib.lc_amd_maskcrop_source_hash().decode() == build.source_hash(T) == build.embedded_hash(T.so_path, T.hash_marker)
     assert build.sources(T) == [os.path.join(build.CSRC, "maskcrop", "lc_maskcrop.hip")]
-
-    def mine(d):
-        return os.sep + "maskcrop" + os.sep in d or d.endswith("lc_amd_maskcrop.h")
-
-    for t in others:  # no other library sees this directory or header
-        assert not any(mine(d) for d in build._deps(t)), t.name
-    assert all(mine(d) or d in (build.WARP_GRID_H, build.WAVE_INT_H) for d in build._deps(T))  # its own, or exactly the shared headers it declares
-    src = open(build.sources(T)[0]).read()
-    assert set(re.findall(r'#include "([^"]+)"', src)) == {"../../../include/lc_amd_maskcrop.h", "../shared/lc_warp_grid.h", "../shared/lc_wave_int.h"}
-    doc = build.__doc__
-    assert "liblc_amd_maskcrop.so" in doc and "lc_amd/csrc/maskcrop/" in doc and "include/lc_amd_maskcrop.h" in doc
 
     header = open(os.path.join(ROOT, "include", "lc_amd_maskcrop.h")).read()
     text = re.sub(r"/\*.*?\*/", "", header, flags=re.S)

@@ -79,7 +79,6 @@ def test_shared_loader_refuses_what_it_cannot_rebuild(tmp_path, monkeypatch):
         assert msg.startswith(f"lc_amd: {target.so_path} was built from other sources than the ones next to it (embedded hash None, "
                               f"sources {build.source_hash(build.MODELS)}) and hipcc is not available")
     assert not any(build.source_hash(t) in msg for t in build.TARGETS if t is not build.MODELS)
-    assert len([t for t in build.TARGETS if t is not build.MODELS]) == 11
 
 
 def test_source_hash_covers_the_shared_cross_lane_header():
@@ -87,5 +86,3 @@ def test_source_hash_covers_the_shared_cross_lane_header():
 
     deps = build._deps(build.MODELS)
     assert build.SHARED_H in deps and os.path.join(ROOT, "include", "lc_amd_models.h") in deps
-    src = open(build.sources(build.MODELS)[0]).read()
-    assert re.findall(r'#include "([^"]+)"', src) == ["../../../include/lc_amd_models.h", "../shared/lc_shared.h"]

@@ -42,17 +42,10 @@ def test_embedded_source_hash_and_separate_sources():
     lib = render.load()
     assert lib.lc_amd_render_source_hash().decode() == build.source_hash(build.RENDER) == build.embedded_hash(build.RENDER.so_path, build.RENDER.hash_marker)
     assert build.sources(build.RENDER) == [os.path.join(build.CSRC, "render", "lc_render.hip")]
-    # the one registry: its first five libraries in build order, twelve different hashes; no other library sees this directory or header
-    assert build.TARGETS[:5] == (build.MAIN, build.OPTIM, build.POSECOV, build.RENDER, build.CROP)
-    others = [t for t in build.TARGETS if t is not build.RENDER]
-    assert len(others) == 11
-    for t in others:
-        assert not any("render" in os.path.basename(s) or os.sep + "render" + os.sep in s for s in build._deps(t))
-    assert len({build.source_hash(t) for t in build.TARGETS}) == 12
-    for t in others:  # their libraries, as built, still carry the hash of their sources
-        assert build.embedded_hash(t.so_path, t.hash_marker) in (None, build.source_hash(t))
-    src = open(build.sources(build.RENDER)[0]).read()
-    assert re.findall(r'#include "([^"]+)"', src) == ["../../../include/lc_amd_render.h"]
+    for t in build.TARGETS:  # no other library hashes a file with this one's name in it (its directory and header: tests/test_libraries_host.py)
+        assert t is build.RENDER or not any("render" in os.path.basename(s) for s in build._deps(t))
+    for t in build.TARGETS:  # the other libraries, as built, still carry the hash of their sources
+        assert t is build.RENDER or build.embedded_hash(t.so_path, t.hash_marker) in (None, build.source_hash(t))
 
 
 def _call(lib, **over):

@@ -135,34 +135,16 @@ def test_oracle_closed_forms():
 # ---- the library
 
 
-def test_build_group_header_exports_and_source_hash(monkeypatch):
+def test_build_group_header_exports_and_source_hash():
     import __graft_entry__ as entry
     from lc_amd import build, rle
 
-    T = build.RLE
-    others = [t for t in build.TARGETS if t is not T]
-    assert build.TARGETS[11] is T and len(others) == 11 and build.TARGETS[10] is build.AUGMENT and len(build.TARGETS[:10]) == 10
-    assert T.so_path.endswith(os.path.join("_C", "liblc_amd_rle.so")) and T.header == "lc_amd_rle.h" and T.shared == ()
-    asked, real = [], build.build
-    monkeypatch.setattr(build, "build", lambda force=False, verbose=False, target=build.MAIN: (asked.append(target), real(force, verbose, target))[1])
+    T = build.RLE  # (its place among the libraries, its files and includes: tests/test_libraries_host.py)
     entry.build()
-    assert tuple(asked[:12]) == build.TARGETS and asked.index(T) == build.TARGETS.index(T) == 11  # built twelfth
-    monkeypatch.undo()
     lib = rle.load()
     assert not build.is_stale(T)
     assert lib.lc_amd_rle_source_hash().decode() == build.source_hash(T) == build.embedded_hash(T.so_path, T.hash_marker)
     assert build.sources(T) == [os.path.join(build.CSRC, "rle", "lc_rle.hip")]
-
-    def mine(d):
-        return os.sep + "rle" + os.sep in d or d.endswith("lc_amd_rle.h")
-
-    for t in others:  # no other library sees this directory or header, or carries this marker
-        assert not any(mine(d) for d in build._deps(t)), t.name
-        assert build.embedded_hash(t.so_path, T.hash_marker) is None, t.name
-    assert all(mine(d) for d in build._deps(T))
-    assert set(re.findall(r'#include "([^"]+)"', open(build.sources(T)[0]).read())) == {"../../../include/lc_amd_rle.h"}
-    doc = build.__doc__
-    assert "liblc_amd_rle.so" in doc and "lc_amd/csrc/rle/" in doc and "include/lc_amd_rle.h" in doc
 
     header = open(os.path.join(ROOT, "include", "lc_amd_rle.h")).read()
     text = re.sub(r"/\*.*?\*/", "", header, flags=re.S)

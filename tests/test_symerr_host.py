@@ -111,14 +111,8 @@ def test_library_header_exports_and_signatures_agree():
     assert not build.is_stale(build.SYMERR)
     assert lib.lc_amd_symerr_source_hash().decode() == build.source_hash(build.SYMERR) == build.embedded_hash(build.SYMERR.so_path, build.SYMERR.hash_marker)
     assert build.sources(build.SYMERR) == [os.path.join(build.CSRC, "symerr", "lc_sym_metrics.hip")]
-    others = [t for t in build.TARGETS if t is not build.SYMERR]
-    assert build.TARGETS.index(build.SYMERR) == 6 and len(others) == 11
-    for t in others:  # no other library sees this directory or header, and this one adds no file to theirs
-        assert not any(os.sep + "symerr" + os.sep in d or d.endswith("lc_amd_symerr.h") for d in build._deps(t)), t.name
-    deps = build._deps(build.SYMERR)  # what the source includes from outside its directory is hashed with it
+    deps = build._deps(build.SYMERR)  # what the source includes from outside its directory is hashed with it (tests/test_libraries_host.py)
     assert os.path.join(build.CSRC, "lc_sym_args.h") in deps and build.SHARED_H in deps
-    src = open(build.sources(build.SYMERR)[0]).read()
-    assert set(re.findall(r'#include "(\.\./[^"]+)"', src)) == {"../../../include/lc_amd_symerr.h", "../lc_sym_args.h", "../shared/lc_shared.h"}
 
 
 def test_entry_point_checks_its_arguments_before_launching():

@@ -1,5 +1,5 @@
 """VSD without a GPU: the wrapper's refusals (lc_amd.vsd), the library of its own (liblc_amd_vsd.so: header, exports, signatures and source
-hash agree; no other library sees its sources; the registry of libraries and its build order), the argument checks of the C entry point before any launch, and the
+hash agree; its place among the libraries: tests/test_libraries_host.py), the argument checks of the C entry point before any launch, and the
 kernels' resources read from the code object (no scratch)."""
 import ctypes
 import os
@@ -19,20 +19,11 @@ def _good(B=3, h=4, w=5):
                 taus=(0.1, 0.2))
 
 
-def test_build_groups(monkeypatch):
+def test_build_groups():
     import __graft_entry__ as entry
     from lc_amd import build
 
-    # the one registry: every library, member by member, in build order
-    assert build.TARGETS == (build.MAIN, build.OPTIM, build.POSECOV, build.RENDER, build.CROP, build.MODELS, build.SYMERR, build.VSD, build.GTINFO,
-                             build.MASKCROP, build.AUGMENT, build.RLE) and len(build.TARGETS) == 12
-    assert [t.name for t in build.TARGETS] == ["main", "optim", "posecov", "render", "crop", "models", "symerr", "vsd", "gtinfo", "maskcrop", "augment", "rle"]
-    assert build.VSD.so_path.endswith(os.path.join("_C", "liblc_amd_vsd.so")) and build.VSD.header == "lc_amd_vsd.h" and build.VSD.shared == (build.RAY_LENGTH_H, build.WAVE_INT_H)
-    # the entry point's build() hands every library to the builder, in the registry's order, and leaves this one in place and current
-    asked, real = [], build.build
-    monkeypatch.setattr(build, "build", lambda force=False, verbose=False, target=build.MAIN: (asked.append(target), real(force, verbose, target))[1])
-    entry.build()
-    assert tuple(asked[:12]) == build.TARGETS
+    entry.build()  # (the registry and the build order: tests/test_libraries_host.py) leaves this library in place and current
     assert os.path.exists(build.VSD.so_path) and not build.is_stale(build.VSD)
 
 
@@ -64,15 +55,6 @@ def test_source_hash_is_its_own():
     assert not build.is_stale(build.VSD)
     assert lib.lc_amd_vsd_source_hash().decode() == build.source_hash(build.VSD) == build.embedded_hash(build.VSD.so_path, build.VSD.hash_marker)
     assert build.sources(build.VSD) == [os.path.join(build.CSRC, "vsd", "lc_vsd.hip")]
-    others = [t for t in build.TARGETS if t is not build.VSD]
-    assert len(others) == 11
-    for t in others:  # no other library sees this directory or header, and this one adds no file to theirs
-        assert not any(os.sep + "vsd" + os.sep in d or d.endswith("lc_amd_vsd.h") for d in build._deps(t)), t.name
-        assert build.embedded_hash(t.so_path, build.VSD.hash_marker) is None, t.name
-    # every dependency is the library's own, or one of exactly the shared headers it declares
-    assert all(os.sep + "vsd" + os.sep in d or d.endswith("lc_amd_vsd.h") or d in (build.RAY_LENGTH_H, build.WAVE_INT_H) for d in build._deps(build.VSD))
-    src = open(build.sources(build.VSD)[0]).read()
-    assert set(re.findall(r'#include "([^"]+)"', src)) == {"../../../include/lc_amd_vsd.h", "../shared/lc_ray_length.h", "../shared/lc_wave_int.h"}
     assert not os.path.exists(os.path.join(build.CSRC, "render", "lc_vsd.hip"))
 
 
