@@ -14,14 +14,18 @@
     augment  lc_amd/_C/liblc_amd_augment.so  lc_amd/csrc/augment/     include/lc_amd_augment.h  the training crops' background switch and colour augmentation
     rle      lc_amd/_C/liblc_amd_rle.so      lc_amd/csrc/rle/         include/lc_amd_rle.h      the store of COCO run-length masks: index, decode, encode
     geometry lc_amd/_C/liblc_amd_geometry.so lc_amd/csrc/geometry/    include/lc_amd_geometry.h the training crops' geometry drawn from the seed word
+    bgstore  lc_amd/_C/liblc_amd_bgstore.so  lc_amd/csrc/bgstore/     include/lc_amd_bgstore.h  the resident background store: each row's pick, cut and blend
 
 A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`): code that
 two libraries need exists once there (lc_shared.h: main, posecov, models, symerr; lc_warp_grid.h: crop, maskcrop; lc_ray_length.h: vsd,
 gtinfo; lc_wave_int.h: vsd, gtinfo, maskcrop; lc_keyed_hash.h: maskcrop, augment, geometry; lc_byte_finish.h: crop, augment), and no side
 library restates another's arithmetic -- but for the wave scans that rle writes out for itself.  `TARGETS` is every library in build
 order: whoever builds, packages, hashes or compares "all of them" iterates it, and tests/test_libraries_host.py states it row by row
-(each library's files, marker, shared headers and includes, and each shared header's users).  Every function takes the library it
-works on as a `Target` (default: the hot-path library)."""
+(each library's files, marker, shared headers and includes, and each shared header's users).  `LATER_TARGETS` holds the libraries added
+since that statement was written (bgstore, which includes lc_keyed_hash.h and lc_warp_grid.h and restates crop's tap combination and
+augment's blend, pinned by tests/test_gpu_bgstore.py): "all of them" is `TARGETS + LATER_TARGETS`, in that order, and `build_later`
+builds the second tuple as `build` builds a member of the first.  Every function takes the library it works on as a `Target`
+(default: the hot-path library)."""
 from __future__ import annotations
 
 import glob
@@ -90,6 +94,10 @@ RLE = _side("rle")  # the training loader's device-resident store of run-length 
 GEOMETRY = _side("geometry", (KEYED_HASH_H,))  # the training loader's geometry drawn on the device from the seed word (lc_amd.geometry)
 # every library, in build order
 TARGETS = (MAIN, OPTIM, POSECOV, RENDER, CROP, MODELS, SYMERR, VSD, GTINFO, MASKCROP, AUGMENT, RLE, GEOMETRY)
+# the training loader's resident background store (lc_amd.backgrounds); takes its coordinates from CROP's header and its hash from MASKCROP's
+BGSTORE = _side("bgstore", (KEYED_HASH_H, WARP_GRID_H))
+# the libraries that came after the registry test's rows, in build order behind TARGETS (folding the two tuples: DESIGN.md, section 7)
+LATER_TARGETS = (BGSTORE,)
 HASH_MARKER = MAIN.hash_marker
 
 
@@ -153,10 +161,19 @@ def _locked(fn, target: Target = MAIN):
         return fn()
 
 
-def build(force: bool = False, verbose: bool = False, target: Target = MAIN) -> str:
+def _build_one(force: bool, verbose: bool, target: Target) -> str:
     if not force and not is_stale(target):
         return target.so_path
     return _locked(lambda: target.so_path if (not force and not is_stale(target)) else _compile(target.so_path, [], verbose, target), target)
+
+
+def build(force: bool = False, verbose: bool = False, target: Target = MAIN) -> str:
+    return _build_one(force, verbose, target)
+
+
+def build_later(force: bool = False, verbose: bool = False) -> list:
+    """Every library of `LATER_TARGETS`, in order, each as `build` builds one."""
+    return [_build_one(force, verbose, t) for t in LATER_TARGETS]
 
 
 # Extra compiler flags of single translation units.  The latency builds of the one-wave pose kernels are scheduled for the shortest
@@ -246,3 +263,5 @@ def build_variant(name: str, flags, verbose: bool = False) -> str:
 if __name__ == "__main__":
     for t in TARGETS:
         print(build(force=True, verbose=True, target=t))
+    for path in build_later(force=True, verbose=True):
+        print(path)

@@ -2,8 +2,8 @@
 (`dataset.py:402-470`), from frames, masks, boxes and cameras that already lie on the device and ONE 64-bit seed word.
 
     train_inputs(frames, frame_index, *, masks=None, rle_store=None, mask_index=None, bbox_xyxy, cam_K, sample_id, cfg, seed,
-                 backgrounds=None, in_hw, out_hw, valid_th=100, n_check=256, vis_interp="linear", dtype=torch.float32, normalize=None,
-                 meshes=None, mesh_index=None, R=None, t=None, near=None, far=None, geometry=None) -> dict
+                 backgrounds=None, background_store=None, in_hw, out_hw, valid_th=100, n_check=256, vis_interp="linear", dtype=torch.float32,
+                 normalize=None, meshes=None, mesh_index=None, R=None, t=None, near=None, far=None, geometry=None) -> dict
 
 Pure Python over the wrappers of the loader's stages, in this order, all on the current stream:
 
@@ -12,18 +12,21 @@ Pure Python over the wrappers of the loader's stages, in this order, all on the 
     3. maskcrop.mask_crops             msk_vis, msk_noc, valid_cnt, sym_ck_pts2d with out_affine; the check points of sample `step_id`
     4. maskcrop.mask_crops             msk_in with in_affine (the mask the background switch blends with)
     5. crops.warp_affine               the uint8 crop of the frame with in_affine
-    6. augment.augment_drawn           rgb_in: the background switch and the colour chain, drawn from the same seed word
+    6. augment.augment_drawn           rgb_in: the background switch and the colour chain, drawn from the same seed word; with a
+                                       `backgrounds.BackgroundStore`, backgrounds.switch_backgrounds picks, cuts and blends each row's
+                                       background in the uint8 crop first, and the colour chain follows without a switch of its own
     7. render.render_homo_z_out        homo_z_out with the device's out_K, where meshes are given
 
 Nothing is formed on the host and nothing is read back, so the whole call can be captured with `torch.cuda.graph`; the word `seed` names
 is read by the kernels of stages 1 and 6 at every replay, and stage 3's check points follow through `step_id`: after `seed.add_(1)` a
-replay redraws geometry, check points and colours.  It adds no kernel of its own."""
+replay redraws geometry, check points, colours and, with a store, each row's background and its region.  It adds no kernel of its own."""
 from __future__ import annotations
 
 import torch
 from torch import Tensor
 
 from . import _args, augment, crops, maskcrop, render, rle
+from . import backgrounds as _backgrounds
 from . import geometry as _geometry
 from .augment import AugmentConfig
 
@@ -42,13 +45,14 @@ def _batch(**named) -> int:
 
 @torch.no_grad()
 def train_inputs(frames, frame_index, *, masks=None, rle_store=None, mask_index=None, bbox_xyxy, cam_K, sample_id, cfg: AugmentConfig, seed,
-                 backgrounds=None, in_hw, out_hw, valid_th=100, n_check=256, vis_interp="linear", dtype=torch.float32, normalize=None,
-                 meshes=None, mesh_index=None, R=None, t=None, near=None, far=None, geometry=None) -> dict:
+                 backgrounds=None, background_store=None, in_hw, out_hw, valid_th=100, n_check=256, vis_interp="linear", dtype=torch.float32,
+                 normalize=None, meshes=None, mesh_index=None, R=None, t=None, near=None, far=None, geometry=None) -> dict:
     """frames (F,H,W,3) uint8 and frame_index (B,) int32; the visible masks as bytes `masks` (F',H,W) uint8 / bool, or as `rle_store`, an
     `rle.RleStore` of masks of the frames' size that is decoded to full frames -- one of the two -- with mask_index (B,) int32 (None: row b
     reads mask b); bbox_xyxy (B,4) float32, cam_K (B,3,3) or (3,3) float32, sample_id (B,) int32; cfg an AugmentConfig; seed a device
     tensor of one uint64 / int64 element (or a whole number, which fixes the draw); backgrounds (G,3,h,w) uint8 already cut to the
-    input size, or None; in_hw and out_hw = (h, w) of the network's input and output; valid_th, n_check, vis_interp as `mask_crops`
+    input size, or background_store, a `backgrounds.BackgroundStore` of images of their own sizes from which every row's background is
+    picked and cut anew at every step -- at most one of the two; in_hw and out_hw = (h, w) of the network's input and output; valid_th, n_check, vis_interp as `mask_crops`
     takes them, dtype and normalize as `augment_drawn` does; meshes a `render.MeshSet` with mesh_index (B,) int32, R (B,3,3), t (B,3) and
     near, far -- all of them or none.  `geometry`: a `geometry.ZoomGeometry` of device tensors to use in the place of stage 1 (what a host
     draw uploads: the route this chain replaces, kept for measuring it); its step_id feeds the check points as ever.
@@ -59,6 +63,10 @@ def train_inputs(frames, frame_index, *, masks=None, rle_store=None, mask_index=
     any stage refused (a refused geometry gives NaN matrices, which every later stage refuses in turn)."""
     if (masks is None) == (rle_store is None):
         raise ValueError("lc_amd.train_inputs: the visible masks come as bytes (masks) or as an RleStore (rle_store): one of the two")
+    if backgrounds is not None and background_store is not None:
+        raise ValueError("lc_amd.train_inputs: the backgrounds come cut to the input size (backgrounds) or as a BackgroundStore (background_store): at most one of the two")
+    if background_store is not None and not isinstance(background_store, _backgrounds.BackgroundStore):
+        raise TypeError(f"lc_amd.train_inputs: background_store must be a BackgroundStore, got {type(background_store)}")
     if rle_store is not None and not isinstance(rle_store, rle.RleStore):
         raise TypeError(f"lc_amd.train_inputs: rle_store must be an RleStore, got {type(rle_store)}")
     with_meshes = meshes is not None
@@ -101,8 +109,12 @@ def train_inputs(frames, frame_index, *, masks=None, rle_store=None, mask_index=
     mi = maskcrop.mask_crops(masks, g.in_affine, (in_h, in_w), mask_index=mask_index, n_check=0, want=("msk_vis",))
     winfo = torch.empty(B, device=dev, dtype=torch.int32)
     crop = crops.warp_affine(frames, g.in_affine, (in_h, in_w), frame_index=frame_index, dtype=torch.uint8, info=winfo)
+    infos += [mc.info, mi.info, winfo]
+    if background_store is not None:
+        sinfo, _ = _backgrounds.switch_backgrounds(crop, background_store, cfg, seed=word, sample_id=sample_id, msk_in=mi.msk_vis)
+        infos.append(sinfo)  # (1 on a switched row: above the 0 of the other stages, so only a refusal shows)
     rgb_in, ainfo = augment.augment_drawn(crop, cfg, seed=word, sample_id=sample_id, msk_in=mi.msk_vis, backgrounds=backgrounds, dtype=dtype, normalize=normalize)
-    infos += [mc.info, mi.info, winfo, ainfo]
+    infos.append(ainfo)
     out = dict(rgb_in=rgb_in, msk_vis=mc.msk_vis, msk_noc=mc.msk_noc, sym_ck_pts2d=mc.sym_ck_pts2d, valid_cnt=mc.valid_cnt, out_K=g.out_K,
                out_pix_scale=g.out_pix_scale, in_affine=g.in_affine)
     if with_meshes:
