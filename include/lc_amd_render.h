@@ -14,7 +14,9 @@
  * (round-half-even), the sample points lie on that grid, and the three edge functions are integer-valued doubles below 2^53.  A
  * sample is covered when all three have the same sign or are zero; zero-area faces cover nothing.  1/z is interpolated with the
  * exact barycentric weights and z rounded once to fp32.  Per pixel the smallest (fp32 bits of z, face index) pair wins, so the
- * result does not depend on the order of evaluation.
+ * result does not depend on the order of evaluation.  near < z < far is tested per sample on that fp32 value: a face whose vertices
+ * pass z > near in fp64 but whose z rounds onto near (or onto far) covers nothing there and is not counted.  A face with a vertex
+ * index outside [0, n_vert) of its mesh covers nothing and is not counted either.
  *
  *   verts (total_verts,3) f32, faces (total_faces,3) int32: the meshes' arrays concatenated; face indices are relative to the mesh
  *   mesh_table (n_meshes,4) int32 on the device: vert_off, n_vert, face_off, n_face

@@ -1,6 +1,7 @@
 """Procedural meshes, poses and cameras of the rasteriser's tests (TEST INFRASTRUCTURE ONLY): no assets.  tests/test_render_oracle.py
 asserts for every case the two conditions tests/test_gpu_render.py relies on (vertex coordinates clear of the snapping boundaries, few
-tie pixels); a case that violates one gets another pose, never a wider cap."""
+tie pixels); a case that violates one gets another pose, never a wider cap.  The rules these cases keep clear of -- samples on edges,
+snapping halves, exact depth ties, near and far themselves -- are decided on the exact scenes of tests/render_grid.py."""
 from __future__ import annotations
 
 import functools
