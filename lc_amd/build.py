@@ -15,6 +15,7 @@
     rle      lc_amd/_C/liblc_amd_rle.so      lc_amd/csrc/rle/         include/lc_amd_rle.h      the store of COCO run-length masks: index, decode, encode
     geometry lc_amd/_C/liblc_amd_geometry.so lc_amd/csrc/geometry/    include/lc_amd_geometry.h the training crops' geometry drawn from the seed word
     bgstore  lc_amd/_C/liblc_amd_bgstore.so  lc_amd/csrc/bgstore/     include/lc_amd_bgstore.h  the resident background store: each row's pick, cut and blend
+    shade    lc_amd/_C/liblc_amd_shade.so    lc_amd/csrc/shade/       include/lc_amd_shade.h    the shading pass behind the rasteriser: uint8 frames of posed, vertex-coloured meshes
 
 A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`): code that
 two libraries need exists once there (lc_shared.h: main, posecov, models, symerr; lc_warp_grid.h: crop, maskcrop; lc_ray_length.h: vsd,
@@ -24,7 +25,10 @@ order: whoever builds, packages, hashes or compares "all of them" iterates it, a
 (each library's files, marker, shared headers and includes, and each shared header's users).  `LATER_TARGETS` holds the libraries added
 since that statement was written (bgstore, which includes lc_keyed_hash.h and lc_warp_grid.h and restates crop's tap combination and
 augment's blend, pinned by tests/test_gpu_bgstore.py): "all of them" is `TARGETS + LATER_TARGETS`, in that order, and `build_later`
-builds the second tuple as `build` builds a member of the first.  Every function takes the library it works on as a `Target`
+builds the second tuple as `build` builds a member of the first.  `EXTRA_TARGETS` is where every library after that goes (shade, which
+includes no shared header and restates the rasteriser's snapped projection, pinned by tests/test_gpu_shade.py): "all of them" is
+`TARGETS + LATER_TARGETS + EXTRA_TARGETS`, `build_later` builds the third tuple behind the second, and the next library joins the third
+tuple.  Every function takes the library it works on as a `Target`
 (default: the hot-path library)."""
 from __future__ import annotations
 
@@ -98,6 +102,9 @@ TARGETS = (MAIN, OPTIM, POSECOV, RENDER, CROP, MODELS, SYMERR, VSD, GTINFO, MASK
 BGSTORE = _side("bgstore", (KEYED_HASH_H, WARP_GRID_H))
 # the libraries that came after the registry test's rows, in build order behind TARGETS (folding the two tuples: DESIGN.md, section 7)
 LATER_TARGETS = (BGSTORE,)
+SHADE = _side("shade")  # the shading pass behind the rasteriser (lc_amd.shade); includes no shared header
+# every library added since, in build order behind LATER_TARGETS: the tuple the next library joins
+EXTRA_TARGETS = (SHADE,)
 HASH_MARKER = MAIN.hash_marker
 
 
@@ -172,8 +179,8 @@ def build(force: bool = False, verbose: bool = False, target: Target = MAIN) -> 
 
 
 def build_later(force: bool = False, verbose: bool = False) -> list:
-    """Every library of `LATER_TARGETS`, in order, each as `build` builds one."""
-    return [_build_one(force, verbose, t) for t in LATER_TARGETS]
+    """Every library of `LATER_TARGETS` and then of `EXTRA_TARGETS`, in order, each as `build` builds one."""
+    return [_build_one(force, verbose, t) for t in LATER_TARGETS + EXTRA_TARGETS]
 
 
 # Extra compiler flags of single translation units.  The latency builds of the one-wave pose kernels are scheduled for the shortest

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Is the device code of two trees the same?  The proof a refactor of the kernels' sources rests on: the gfx950 assembly of every
-translation unit of every library (lc_amd/build.py: TARGETS and LATER_TARGETS), compiled from each tree, compared by hash.  Needs hipcc, no GPU.
+translation unit of every library (lc_amd/build.py: TARGETS, LATER_TARGETS and EXTRA_TARGETS), compiled from each tree, compared by hash.  Needs hipcc, no GPU.
 
     python scripts/isa_identity.py BEFORE AFTER [> profiles/<topic>/isa_identity.txt]
 
@@ -40,7 +40,7 @@ def main(argv):
     if len(argv) != 3:
         sys.exit(__doc__)
     before, after = (os.path.abspath(a) for a in argv[1:])
-    units = [(os.path.relpath(src, ROOT), t.hash_marker.decode().rstrip(":")) for t in build.TARGETS + build.LATER_TARGETS for src in build.sources(t)]
+    units = [(os.path.relpath(src, ROOT), t.hash_marker.decode().rstrip(":")) for t in build.TARGETS + build.LATER_TARGETS + build.EXTRA_TARGETS for src in build.sources(t)]
     units.sort()
 
     def one(unit):
