@@ -41,6 +41,16 @@ __device__ __forceinline__ double fast_sqrt(double x) {
     return s;
 }
 
+// The same for x > 0 only (the caller has tested it): the arithmetic of fast_sqrt_rsqrt without its compare and its two 64-bit selects
+// for x == 0 -- the same bits wherever x > 0.
+__device__ __forceinline__ void fast_sqrt_rsqrt_pos(double x, double& s, double& rs) {
+    const double r0 = __builtin_amdgcn_rsq(x);
+    const double g = x * r0, h = 0.5 * r0;
+    const double rr = __builtin_fma(-h, g, 0.5);
+    s = __builtin_fma(g, rr, g);
+    rs = 2.0 * __builtin_fma(h, rr, h);
+}
+
 // Ordering point between the lanes of ONE wavefront that hand data to each other through LDS.  The wave barrier alone is a
 // scheduling barrier (IntrNoMem); the wavefront-scope release / acquire pair around it makes the hand-off part of the memory
 // model -- the compiler may not move a lane's ds_read above another lane's ds_write across it -- and emits no instruction on

@@ -85,19 +85,29 @@ struct Rot {
 };
 
 __device__ __forceinline__ void make_rot(const double aa[3], Rot& o) {
-    // branch-free on purpose: a two-branch version keeps `o` in scratch memory (104 B/lane of HBM traffic per evaluation)
+    // aa is WAVE-UNIFORM (the pose every lane carries), so the two cases of ceres/rotation.h are a scalar branch: uniform() is an any-lane
+    // ballot, and a caller whose lanes hold different poses would send all of them down the small arm as soon as one is small.
+    // Found: such a uniform branch keeps the rotation in registers -- no kernel of the library gains a byte of scratch (a per-lane branch
+    // had put `o` there) -- as long as the coefficients leave both arms through the same four locals and R, Jr are formed once behind it.
+    // Bits: each arm evaluates the expressions of the former branch-free form with its selected values, the small arm 0 * x * y - 1 * z
+    // and so on with the products of zeros left in, so signed zeros and non-finite inputs come out as before.
     const double x = aa[0], y = aa[1], z = aa[2];
     const double th2 = x * x + y * y + z * z;
     const bool small = !(th2 > DBL_EPSILON);  // ceres/rotation.h AngleAxisRotatePoint: pt + aa x pt, derivative -[pt]x
-    double th, ith;
-    fast_sqrt_rsqrt(th2, th, ith);
-    double s, c;
-    sincos_small(th, s, c);
-    const double ith2 = ith * ith;
-    const double A = small ? 1.0 : s * ith;
-    const double B = small ? 0.0 : (1.0 - c) * ith2;
-    const double C = small ? 0.0 : (th - s) * ith2 * ith;
-    const double cd = small ? 1.0 : c;
+    double A, B, C, cd;
+    if (__builtin_expect(uniform(small), 0)) {
+        A = 1.0; B = 0.0; C = 0.0; cd = 1.0;
+    } else {
+        double th, ith;
+        fast_sqrt_rsqrt_pos(th2, th, ith);
+        double s, c;
+        sincos_small(th, s, c);
+        const double ith2 = ith * ith;
+        A = s * ith;
+        B = (1.0 - c) * ith2;
+        C = (th - s) * ith2 * ith;
+        cd = c;
+    }
     // R = c I + A [w]x + B w w^T
     o.R[0] = cd + B * x * x;    o.R[1] = B * x * y - A * z; o.R[2] = B * x * z + A * y;
     o.R[3] = B * x * y + A * z; o.R[4] = cd + B * y * y;    o.R[5] = B * y * z - A * x;
@@ -175,16 +185,46 @@ __device__ __forceinline__ void accumulate_point(const Point& pt, const Rot& rt,
     }
 }
 
-// solve (A + diag(dg)) y = rhs for symmetric A (packed upper 21) by LDL^T; false if a pivot is not positive/finite
+// v_min_f64 / v_max_f64 as the instructions they are (clamp_diag below has the reason: fmin / fmax put a canonicalising v_max_f64 x, x in
+// front wherever the compiler cannot see that x is no signalling NaN).  IEEE mode, the kernels' default: a quiet NaN operand gives the other.
+__device__ __forceinline__ double min_f64(double a, double b) {
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ double max_f64(double a, double b) {
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// solve (A + diag(dg)) y = rhs for symmetric A (packed upper 21) by LDL^T; false if a pivot is not positive/finite -- or, with RUNNING,
+// true with a NaN y (below), which the caller's test of the model cost change turns down
+template <bool RUNNING>
 __device__ __forceinline__ bool ldlt_solve6(const double (&A)[21], const double (&dg)[6], const double (&rhs)[6], double (&y)[6]) {
     double L[6][6], Ld[6][6], id[6];
-    bool ok = true;
+    // RUNNING: the pivots are not tested one by one (two compares and two mask operations each, holding VCC between dependent arithmetic of
+    // a phase that is bound by issue): their running minimum and maximum are kept beside the factorisation and tested once.  v_min_f64 /
+    // v_max_f64 return the OTHER operand for a quiet NaN, so over the pivots that are not NaN the two are exact (the pivots are results
+    // of additions and multiplications, never signalling NaNs), and `lo > 0 && hi < DBL_MAX` is `every such pivot is > 0 and < DBL_MAX`.
+    // A NaN pivot is dropped by them -- lo and hi start from d0 itself, not from a constant, so a NaN d0 is replaced by the next pivot that
+    // is not NaN, and six NaN pivots fail `lo > 0` -- and needs no test of its own: id[j] = fast_rcp(NaN) is NaN, so y[j] = z[j] * id[j] - ...
+    // is NaN, so every y[i] with i <= j is (y[i] subtracts L[j][i] * y[j]), so the caller's model cost change is NaN and its `mcc > 0`
+    // false: the step is invalid as it was when the pivot test said so.  The only reader of the result is that conjunction.
+    // !RUNNING: each pivot as it appears, the result in a scalar mask: for the kernel whose registers are full (FormDefaults::PIVOTS_RUNNING).
+    [[maybe_unused]] double lo = 0, hi = 0;
+    [[maybe_unused]] bool each = true;
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
         double dj = A[tri6(j, j)] + dg[j];
 #pragma unroll
         for (int k = 0; k < j; ++k) dj -= L[j][k] * Ld[j][k];
-        ok = ok && (dj > 0) && (dj < DBL_MAX);
+        if constexpr (RUNNING) {
+            lo = j == 0 ? dj : min_f64(lo, dj);
+            hi = j == 0 ? dj : max_f64(hi, dj);
+        } else {
+            each = each && (dj > 0) && (dj < DBL_MAX);
+        }
         id[j] = fast_rcp(dj);
 #pragma unroll
         for (int i = j + 1; i < 6; ++i) {
@@ -195,6 +235,7 @@ __device__ __forceinline__ bool ldlt_solve6(const double (&A)[21], const double 
             L[i][j] = v * id[j];
         }
     }
+    const bool ok = RUNNING ? (lo > 0) && (hi < DBL_MAX) : each;
     double z[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
@@ -323,9 +364,13 @@ __device__ __forceinline__ double norm6(const double (&v)[6]) {
 struct FormDefaults {
     static constexpr int NW = 1, PPT = 0, SPLIT = 0, TEAM = -1;
     static constexpr bool REG = true, OPTS = false, TRACE = false, TAIL = false;
+    // the LDL^T tests the running minimum and maximum of its pivots once (ldlt_solve6); false: each pivot as it appears -- the same
+    // decision, for the one kernel that has no two register pairs to spare in the factorisation: lc_pnp_lm_kernel at two waves per SIMD
+    // (256 registers, no AGPRs) sends 20-28 B per lane to scratch with the running form, reloaded in every evaluation
+    static constexpr bool PIVOTS_RUNNING = true;
 };
-template <bool O = false>
-struct OneWave : FormDefaults { static constexpr bool OPTS = O; };                        // form 1
+template <bool O = false, bool PR = true>
+struct OneWave : FormDefaults { static constexpr bool OPTS = O, PIVOTS_RUNNING = PR; };   // form 1
 template <int W>
 struct TeamWave : FormDefaults { static constexpr int TEAM = W; };                        // form 2, wave W of the team
 struct OneWaveTrace : FormDefaults { static constexpr bool TRACE = true; };               // form 1, diagnostic
@@ -584,7 +629,7 @@ __device__ __forceinline__ void solve_pose(const PnpParams& p, int b, int lane, 
 #pragma unroll
         for (int i = 0; i < 6; ++i) dg[i] = clamp_diag(H[tri6(i, i)]) * inv_radius;
         LC_PSTAMP(1);
-        bool step_ok = ldlt_solve6(H, dg, g, y);
+        bool step_ok = ldlt_solve6<F::PIVOTS_RUNNING>(H, dg, g, y);
         LC_PSTAMP(6);
         // model_cost_change = y.g - y^T H y / 2 with (H + D) y = g  =>  (y.g + sum d_i y_i^2) / 2   (step = -y)
         double mcc = 0;

@@ -23,7 +23,10 @@ __global__ __launch_bounds__(TEAM ? 128 : 64, WPS) void lc_pnp_lm_kernel(const P
         else pnp::solve_pose<pnp::TeamWave<1>>(p, blockIdx.x, lane, bc, false);
     } else {
         __shared__ __attribute__((aligned(16))) double bc[pnp::kPnpLdsDoubles<1>];
-        pnp::solve_pose<pnp::OneWave<OPTS>>(p, blockIdx.x, threadIdx.x, bc);
+        // WPS == 2 keeps the per-pivot test of the LDL^T (FormDefaults::PIVOTS_RUNNING): with the running form this kernel, and only this
+        // one, spills (scripts/kernel_resources.py: scratch 20-28 B).  Once it has two register pairs to spare, pass `true` here and
+        // remove the flag and the per-pivot arm of ldlt_solve6: no other kernel uses them.
+        pnp::solve_pose<pnp::OneWave<OPTS, WPS == 1>>(p, blockIdx.x, threadIdx.x, bc);
     }
 }
 

@@ -3,11 +3,16 @@
 candidate evaluation, round the loop, to the v_rsq_f64 of the next make_rot.  The path is stated, not guessed: every conditional branch met
 takes the next letter of DECISIONS (T = taken, N = falls through), unconditional branches are followed, and each one is printed with its line
 so that the walk can be checked against the listing.
-    python scripts/isa_lm_path.py FILE.s START_LINE DECISIONS          (profiles/lmstep/NOTES.md has the two walks on record)"""
+    python scripts/isa_lm_path.py FILE.s START_LINE DECISIONS          (profiles/lmstep/NOTES.md has the two walks on record)
+A fourth argument replaces the instruction the walk stops at (a prefix of its mnemonic).  With s_memtime and the assembly of a -DLC_STAMPS
+build, a walk from the line behind one stamp runs to the next stamp: ONE PHASE, make_rot or the LDL^T, as the stamps delimit it (they are
+scheduling barriers, so nothing of a neighbouring phase is interleaved; the stamp's own s_waitcnt is the first line to start behind).
+    python scripts/isa_lm_path.py FILE.s START_LINE DECISIONS s_memtime  (profiles/makerot/NOTES.md)"""
 import re
 import sys
 
 path, start, decisions = sys.argv[1], int(sys.argv[2]), sys.argv[3]
+stop = sys.argv[4] if len(sys.argv) > 4 else "v_rsq_f64"
 lines = open(path).read().split("\n")
 labels = {m.group(1): i for i, l in enumerate(lines) if (m := re.match(r"^(\.LBB\d+_\d+):", l))}
 CLASSES = ["fp64 arithmetic", "  of it: v_max x, x (canonicalise)", "  of it: v_max / v_min", "v_mov / v_cndmask", "v_cmp + SALU mask work", "branches", "  of them taken",
@@ -21,7 +26,7 @@ while True:
         continue
     op, *rest = l.split(None, 1)
     args = rest[0] if rest else ""
-    if op.startswith("v_rsq_f64"):
+    if op.startswith(stop):
         break
     total += 1
     if op in ("s_branch",) or op.startswith("s_cbranch"):
@@ -35,7 +40,7 @@ while True:
             i = labels[args.strip()]
     elif op in ("s_waitcnt", "s_nop"):
         count["waits and nops"] += 1
-    elif op.startswith(("v_rcp", "v_sqrt", "v_sin", "v_cos")):
+    elif op.startswith(("v_rcp", "v_rsq", "v_sqrt", "v_sin", "v_cos")):
         count["transcendental"] += 1
     elif re.match(r"v_(add|mul|fma|fmac|max|min|div_\w+)_f64", op):
         count["fp64 arithmetic"] += 1
