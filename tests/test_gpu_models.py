@@ -1,6 +1,11 @@
 """lc_amd.models on the MI355X: every output bit-equal to the numpy restatement of its definitions (tests/models_cases.py) at the sizes
 around every boundary of the kernels -- the diameter's tile edge (models.DIAM_TILE), the register-resident limit of the farthest-point
-selection (models.FPS_RESIDENT) -- and on inputs where every tie rule fires."""
+selection (models.FPS_RESIDENT), with the diameter on both sides of it -- and on `tied_cases`: exact lattice inputs whose ties are placed
+so that each merge level is asked to break one (a lane's two slots, the two waves of a tile, the tile's key, the partials in tile
+order, the reducer's second round and its j across threads; the selection's 16 waves and its register slots or strided visits),
+singly and as one set.  tests/test_models_host.py shows that each of these inputs tells the planted wrong merges from the definition.
+Not reached: the reducer's in-thread `k == bk && r.z < bjv`, which needs two tiles of one tile row 256 tile numbers apart, that is a
+mesh of more than 256 tile rows (65537 vertices, 2e9 pairs for the oracle)."""
 import ctypes
 
 import numpy as np
@@ -36,6 +41,21 @@ def oracle(cases):
         idx, pts = mc.fps(v, max(counts))
         out[name] = (lo, hi, d, pair, idx, pts)
     return out
+
+
+TIED_PICKS = 64  # the largest fps_count of a tied case: the set takes it for every row, a case alone its own (a prefix)
+
+
+@pytest.fixture(scope="module")
+def tied(models):
+    return mc.tied_cases(models.DIAM_TILE, models.FPS_RESIDENT)
+
+
+@pytest.fixture(scope="module")
+def tied_oracle(tied):
+    """name -> (lo, hi, diameter, pair, fps index and points at TIED_PICKS picks): computed once, shared, read only."""
+    assert all(c.fps_count <= TIED_PICKS <= len(c.verts) for c in tied.values())
+    return {name: (*mc.extents(c.verts), *mc.diameter(c.verts), *mc.fps(c.verts, TIED_PICKS)) for name, c in tied.items()}
 
 
 def _mesh_set(*verts):
@@ -78,6 +98,45 @@ def test_single_mesh_equals_the_oracle_bit_for_bit(models, cases, oracle, name):
         assert _same(info.fps, pts[None, :c])
 
 
+def _assert_row(info, k, ref, count):
+    lo, hi, d, pair, idx, pts = ref
+    assert _same(info.lo[k], lo) and _same(info.hi[k], hi)
+    assert _same(info.diameter[k:k + 1], np.asarray([d], np.float32)), (info.diameter[k].item(), float(d))
+    assert info.pair[k].cpu().tolist() == list(pair)
+    assert info.fps_index[k].cpu().tolist() == idx[:count].tolist()
+    assert _same(info.fps[k], pts[:count])
+
+
+def test_tied_case_names_follow_the_exported_constants(models, tied):
+    assert tuple(tied) == mc.TIED_NAMES
+    T, R = models.DIAM_TILE, models.FPS_RESIDENT
+    assert [len(tied[n].verts) for n in ("lane-slots", "waves", "tile-order", "reduce-two-rounds", "fps-ties-streaming")] == [T, T, 4 * T + 76, 23 * T + 1, R + 300]
+    assert 2 * 1024 < len(tied["fps-ties-resident"].verts) < 3 * 1024 <= R  # three register slots, the last partly filled
+
+
+@pytest.mark.parametrize("name", mc.TIED_NAMES)
+def test_tied_case_equals_the_oracle_bit_for_bit(models, tied, tied_oracle, name):
+    """Exact ties placed at one merge level each (`forces`): the definition's smallest (i, j) and smallest index, not a merge's own order."""
+    c = tied[name]
+    info = models.prepare(_mesh_set(c.verts), c.fps_count)
+    print(name, c.forces, "pair", info.pair.cpu().tolist()[0], "first picks", info.fps_index[0, :4].cpu().tolist())
+    _assert_row(info, 0, tied_oracle[name], c.fps_count)
+    if c.pair is not None:
+        assert tuple(info.pair.cpu().tolist()[0]) == c.pair
+
+
+def test_tied_cases_as_one_shuffled_set(models, tied, tied_oracle):
+    """All tied cases in one call, in a fixed shuffled order (vertex offsets, partial slots and, for the streaming one, a distance
+    row that is not the first): each row is its single-mesh result and the oracle's."""
+    names = [mc.TIED_NAMES[k] for k in np.random.default_rng(5).permutation(len(mc.TIED_NAMES))]
+    assert names != list(mc.TIED_NAMES) and names.index("fps-ties-streaming") > 0
+    info = models.prepare(_mesh_set(*(tied[n].verts for n in names)), TIED_PICKS)
+    for k, n in enumerate(names):
+        single = models.prepare(_mesh_set(tied[n].verts), TIED_PICKS)
+        assert all(torch.equal(a[k:k + 1], b) for a, b in zip(info, single)), n
+        _assert_row(info, k, tied_oracle[n], TIED_PICKS)
+
+
 def test_tie_rules_on_the_cube(models, cases, oracle):
     """36 index pairs share the largest distance and eight corners the first pick: the smallest (i, j) and the lowest index win."""
     v = cases["cube_duplicates"][0]
@@ -99,9 +158,9 @@ def test_a_set_of_meshes_equals_the_single_mesh_calls(models, cases, oracle):
         lo, hi, d, pair, idx, pts = oracle[n]
         assert _same(info.lo[k], lo) and _same(info.hi[k], hi)
         assert _same(info.fps[k], pts[:3]) and info.fps_index[k].cpu().tolist() == idx[:3].tolist()
-        if d is not None:
-            assert _same(info.diameter[k:k + 1], np.asarray([d], np.float32)) and info.pair[k].cpu().tolist() == list(pair)
-    single = models.prepare(_mesh_set(cases["resident+1"][0]), 3)  # its diameter has no oracle: the set against the mesh alone
+        assert _same(info.diameter[k:k + 1], np.asarray([d], np.float32)) and info.pair[k].cpu().tolist() == list(pair), n
+    assert names[2] == "resident+1" and oracle["resident+1"][2] is not None  # row 2: 33 tile rows among smaller meshes, against the oracle above
+    single = models.prepare(_mesh_set(cases["resident+1"][0]), 3)  # and against the mesh alone
     assert torch.equal(info.diameter[2:3], single.diameter) and torch.equal(info.pair[2:3], single.pair)
 
 
@@ -127,6 +186,30 @@ def test_streaming_form_prefix_and_counts(models, cases):
     a, b = models.prepare(ms, 40, want_diameter=False), models.prepare(ms, 16, want_diameter=False)
     assert a.fps_index.cpu().tolist() == [idx.tolist()] and _same(a.fps, pts[None])
     assert torch.equal(a.fps[:, :16], b.fps)
+
+
+def test_two_streaming_meshes_around_a_resident_one(models, cases, oracle, tied, tied_oracle):
+    """Two streaming rows of different lengths, so that the second one's distances start at its own row of the workspace
+    (`mind + m * mind_stride`), at one pick -- the distances are never written -- and at 40: each row is its single-mesh oracle result."""
+    R = models.FPS_RESIDENT
+    a, b, c = cases["resident+1"][0], cases["V65"][0], tied["fps-ties-streaming"].verts
+    assert (len(a), len(b), len(c)) == (R + 1, 65, R + 300)
+    idx_a, pts_a = mc.fps(a, 40)
+    refs = (oracle["resident+1"][:4] + (idx_a, pts_a), oracle["V65"], tied_oracle["fps-ties-streaming"])
+    ms = _mesh_set(a, b, c)
+    for count in (1, 40):
+        info = models.prepare(ms, count)
+        for k, ref in enumerate(refs):
+            _assert_row(info, k, ref[:4] + (ref[4][:count], ref[5][:count]), count)
+
+
+def test_streaming_form_takes_every_vertex_once(models, cases):
+    """fps_count = V past the resident limit: a permutation of the vertices, the oracle's."""
+    v = cases["resident+1"][0]
+    idx, pts = mc.fps(v, len(v))
+    full = models.prepare(_mesh_set(v), len(v), want_diameter=False)
+    got = full.fps_index.cpu().numpy()[0]
+    assert np.array_equal(np.sort(got), np.arange(len(v))) and np.array_equal(got, idx) and _same(full.fps, pts[None])
 
 
 def test_each_part_is_skipped_through_its_null_output(models, cases, oracle):

@@ -210,3 +210,127 @@ def test_prep_models_tool(tmp_path, monkeypatch, capsys):
     assert only.exists() and not (tmp_path / "none.pkl").exists()
     with pytest.raises(FileNotFoundError):
         prep_models.main([str(tmp_path / "empty")])
+
+
+# ---- the tied cases: exact, spanning the merge level they name, and telling every planted mistake from the definition ----
+
+@pytest.fixture(scope="module")
+def tied():
+    """name -> the case with the oracle's answers on it: computed once, shared, read only."""
+    from types import SimpleNamespace
+
+    from lc_amd import models
+
+    out = {}
+    for name, c in mc.tied_cases(models.DIAM_TILE, models.FPS_RESIDENT).items():
+        ties = []
+        idx, pts = mc.fps(c.verts, c.fps_count, ties=ties)
+        top, pairs = mc.maximal_pairs(c.verts)
+        out[name] = SimpleNamespace(case=c, tile=models.DIAM_TILE, diameter=mc.diameter(c.verts), idx=idx, pts=pts, ties=ties, top=top, pairs=pairs)
+    return out
+
+
+def _d2_64(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return ((a - b) ** 2).sum(-1)
+
+
+def test_tied_case_names():
+    from lc_amd import models
+
+    assert tuple(mc.tied_cases(models.DIAM_TILE, models.FPS_RESIDENT)) == mc.TIED_NAMES
+
+
+@pytest.mark.parametrize("name", mc.TIED_NAMES)
+def test_tied_cases_are_exact(tied, name):
+    """Every coordinate is an integer of at most 72 lattice steps, so every d2 is an integer below 3 * 144^2 < 2^24 in lattice units:
+    exact in fp32 whatever the order.  Beside that argument, the fp64 value itself: of every pair of a mesh up to 2500 vertices, of every
+    pair that touches a vertex of a maximal pair in a larger one, and of every distance the selection compares."""
+    t = tied[name]
+    v = t.case.verts
+    steps = v.astype(np.float64) * 2.0 ** mc.LATTICE_BITS
+    assert v.dtype == np.float32 and np.array_equal(steps, np.round(steps)) and np.abs(steps).max() <= 72
+    rows = np.arange(len(v)) if len(v) <= 2500 else np.unique(np.asarray(t.pairs).ravel())
+    for r0 in range(0, len(rows), 256):
+        r = rows[r0:r0 + 256]
+        assert np.array_equal(mc.d2(v[r, None], v[None]).astype(np.float64), _d2_64(v[r, None], v[None]))
+    lo, hi = mc.extents(v)
+    c32, c64 = (lo + hi) * np.float32(0.5), (lo.astype(np.float64) + hi) * 0.5
+    assert np.array_equal(c32.astype(np.float64), c64)
+    m32, m64 = mc.d2(v, c32), _d2_64(v, c64)
+    for k in t.idx:
+        assert np.array_equal(m32.astype(np.float64), m64) and m32.argmax() == k
+        m32, m64 = np.minimum(m32, mc.d2(v, v[k])), np.minimum(m64, _d2_64(v, v[k]))
+
+
+@pytest.mark.parametrize("name", mc.TIED_NAMES)
+def test_tied_cases_span_the_merge_they_name(tied, name):
+    t = tied[name]
+    c = t.case
+    d, pair = t.diameter
+    assert pair == min(t.pairs) and d == np.sqrt(t.top, dtype=np.float32) and mc.diameter_tiled(c.verts, t.tile) == (d, pair)
+    if c.pair is not None:
+        assert pair == c.pair
+    tiles = sorted({mc.tile_number(i, j, t.tile) for i, j in t.pairs})
+    print(f"{name}: {len(c.verts)} vertices, {len(t.pairs)} maximal pairs in {len(tiles)} tiles (numbers {tiles[0]}..{tiles[-1]}), pair {pair}: {c.forces}")
+    if c.spans is not None:
+        assert c.spans(t.pairs)
+    if c.fps_spans:
+        waves = [len({(int(i) // mc.WAVE) % (mc.POINT_THREADS // mc.WAVE) for i in tie}) for tie in t.ties]
+        slots = [len({int(i) // mc.POINT_THREADS for i in tie}) for tie in t.ties]
+        ok = [n for n in range(len(t.ties)) if ("waves" not in c.fps_spans or waves[n] >= 2) and ("slots" not in c.fps_spans or slots[n] >= 2)]
+        assert ok, (waves, slots)
+        n = ok[0]
+        print(f"{name}: pick {n} has {len(t.ties[n])} tied maxima from index {t.ties[n][0]} to {t.ties[n][-1]}, in {waves[n]} waves and {slots[n]} slots; taken: {t.idx[n]}")
+        assert t.idx[n] == t.ties[n][0]
+    if name == "all-identical":
+        lo, hi = mc.extents(c.verts)
+        assert d == 0 and pair == (0, 1) and np.array_equal(lo, hi) and not t.idx.any() and len(t.pairs) == len(c.verts) * (len(c.verts) - 1) // 2
+
+
+@pytest.mark.parametrize("name", mc.TIED_NAMES)
+def test_every_planted_mistake_changes_the_answer(tied, name):
+    """The inputs discriminate: a kernel with one of the case's mistakes could not give the oracle's answer on it."""
+    t = tied[name]
+    c = t.case
+    assert c.mistakes and set(c.mistakes) <= set(mc.DIAMETER_MISTAKES + mc.FPS_MISTAKES)
+    for m in c.mistakes:
+        if m in mc.DIAMETER_MISTAKES:
+            wrong = mc.diameter(c.verts, mistake=m, tile=t.tile)
+            print(f"{name}: {m} gives pair {wrong[1]}, diameter {float(wrong[0])} for {t.diameter[1]}, {float(t.diameter[0])}")
+            assert wrong != t.diameter
+        else:
+            wrong = mc.fps(c.verts, c.fps_count, mistake=m)[0]
+            n = int(np.flatnonzero(wrong != t.idx)[0]) if (wrong != t.idx).any() else None
+            print(f"{name}: {m} first differs at pick {n}")
+            assert n is not None and wrong[n] != t.idx[n]
+
+
+def test_every_mistake_is_detected_by_a_case_and_none_is_on_by_default():
+    from lc_amd import models
+
+    T, R = models.DIAM_TILE, models.FPS_RESIDENT
+    listed = {m for c in mc.tied_cases(T, R).values() for m in c.mistakes}
+    assert listed == set(mc.DIAMETER_MISTAKES + mc.FPS_MISTAKES)
+    with pytest.raises(ValueError):
+        mc.diameter(mc.cloud(5, 1), mistake="none")
+    with pytest.raises(ValueError):
+        mc.fps(mc.cloud(5, 1), 2, mistake="none")
+
+    def fps_as_it_was(v, count):
+        lo, hi = mc.extents(v)
+        mind = mc.d2(v, (lo + hi) * np.float32(0.5))
+        idx = np.empty(count, np.int32)
+        for n in range(count):
+            idx[n] = k = int(mind.argmax())
+            mind = np.minimum(mind, mc.d2(v, v[k]))
+        return idx
+
+    for name, (v, counts, want_d) in mc.named_cases(T, R).items():
+        d, pair = mc.diameter(v)
+        assert mc.diameter(v, mistake=None, tile=T) == (d, pair) == mc.diameter_tiled(v, T), name
+        if 1 < len(v) <= 1100:  # the definition by enumeration: the smallest (i, j) among the pairs of the largest d2
+            top, pairs = mc.maximal_pairs(v)
+            assert pair == min(pairs) and d == np.sqrt(top, dtype=np.float32), name
+        idx, pts = mc.fps(v, max(counts), mistake=None)
+        assert np.array_equal(idx, fps_as_it_was(v, max(counts))) and np.array_equal(pts, v[idx]), name
