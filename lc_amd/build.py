@@ -16,6 +16,7 @@
     geometry lc_amd/_C/liblc_amd_geometry.so lc_amd/csrc/geometry/    include/lc_amd_geometry.h the training crops' geometry drawn from the seed word
     bgstore  lc_amd/_C/liblc_amd_bgstore.so  lc_amd/csrc/bgstore/     include/lc_amd_bgstore.h  the resident background store: each row's pick, cut and blend
     shade    lc_amd/_C/liblc_amd_shade.so    lc_amd/csrc/shade/       include/lc_amd_shade.h    the shading pass behind the rasteriser: uint8 frames of posed, vertex-coloured meshes
+    obox     lc_amd/_C/liblc_amd_obox.so     lc_amd/csrc/obox/        include/lc_amd_obox.h     the oriented model box behind models_xform.json (an offline tool's kernels)
 
 A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`): code that
 two libraries need exists once there (lc_shared.h: main, posecov, models, symerr; lc_warp_grid.h: crop, maskcrop; lc_ray_length.h: vsd,
@@ -26,7 +27,8 @@ order: whoever builds, packages, hashes or compares "all of them" iterates it, a
 since that statement was written (bgstore, which includes lc_keyed_hash.h and lc_warp_grid.h and restates crop's tap combination and
 augment's blend, pinned by tests/test_gpu_bgstore.py): "all of them" is `TARGETS + LATER_TARGETS`, in that order, and `build_later`
 builds the second tuple as `build` builds a member of the first.  `EXTRA_TARGETS` is where every library after that goes (shade, which
-includes no shared header and restates the rasteriser's snapped projection, pinned by tests/test_gpu_shade.py): "all of them" is
+includes no shared header and restates the rasteriser's snapped projection, pinned by tests/test_gpu_shade.py; obox, which includes no
+shared header either and whose fp32 rule is the one of models, pinned by tests/test_gpu_obox.py): "all of them" is
 `TARGETS + LATER_TARGETS + EXTRA_TARGETS`, `build_later` builds the third tuple behind the second, and the next library joins the third
 tuple.  Every function takes the library it works on as a `Target`
 (default: the hot-path library)."""
@@ -104,7 +106,8 @@ BGSTORE = _side("bgstore", (KEYED_HASH_H, WARP_GRID_H))
 LATER_TARGETS = (BGSTORE,)
 SHADE = _side("shade")  # the shading pass behind the rasteriser (lc_amd.shade); includes no shared header
 # every library added since, in build order behind LATER_TARGETS: the tuple the next library joins
-EXTRA_TARGETS = (SHADE,)
+OBOX = _side("obox")  # the oriented model box search (lc_amd.obox, python -m lc_amd.prep_models --xform); includes no shared header
+EXTRA_TARGETS = (SHADE, OBOX)
 HASH_MARKER = MAIN.hash_marker
 
 
