@@ -23,6 +23,7 @@ Call surface (mirrors the reference):
     lc_amd.models.prepare / to_models_info / to_fps_dict   the per-object inputs every path reads: extents, exact diameter, FPS keypoints (liblc_amd_models.so)
     lc_amd.prep_models                   python -m lc_amd.prep_models: models_info.json and the `cfg_global.fps` pickle (dataset.py:232-236) of a directory of meshes
     lc_amd.obox.oriented_box / to_models_xform   <- model_transform.py:21-42 reads it, nothing in the reference writes it: `models_xform.json` (the rigid transform and half-extents of each model's minimum-volume oriented box over a stated grid search; liblc_amd_obox.so; python -m lc_amd.prep_models --xform)
+    lc_amd.symfind.deviation / check_symmetries / propose_symmetries   BOP's geometric rule for a model symmetry (max over the vertices of the distance from the transformed vertex to the nearest one, below max(15 mm, 0.1 diameter)) evaluated on the device: checks the `symmetries_discrete` / `symmetries_continuous` of a models_info.json against the meshes and proposes them for an object that has none (liblc_amd_symfind.so; python -m lc_amd.prep_models --check-symmetries / --symmetries)
     lc_amd.maskcrop.mask_crops           <- dataset.py:414,425-442 (msk_in / msk_vis / msk_noc warps, valid_cnt, sym_ck_pts2d; liblc_amd_maskcrop.so)
     lc_amd.augment.augment / augment_drawn / draw / background_matrices / draw_zoom   <- dataset.py:137-171,313-327,402,413-419 (background switch, colour augmentation, zoom-in box draw; liblc_amd_augment.so)
     lc_amd.backgrounds.BackgroundStore / switch_backgrounds   <- dataset.py:137-148,413-415 (_switch_bg with np.random.choice(self.bg_list): each row's background picked, cut and blended from a resident store; liblc_amd_bgstore.so)

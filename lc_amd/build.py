@@ -17,6 +17,7 @@
     bgstore  lc_amd/_C/liblc_amd_bgstore.so  lc_amd/csrc/bgstore/     include/lc_amd_bgstore.h  the resident background store: each row's pick, cut and blend
     shade    lc_amd/_C/liblc_amd_shade.so    lc_amd/csrc/shade/       include/lc_amd_shade.h    the shading pass behind the rasteriser: uint8 frames of posed, vertex-coloured meshes
     obox     lc_amd/_C/liblc_amd_obox.so     lc_amd/csrc/obox/        include/lc_amd_obox.h     the oriented model box behind models_xform.json (an offline tool's kernels)
+    symfind  lc_amd/_C/liblc_amd_symfind.so  lc_amd/csrc/symfind/     include/lc_amd_symfind.h  the symmetry deviation of a model: BOP's geometric rule, checked and searched (an offline tool's kernels)
 
 A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`): code that
 two libraries need exists once there (lc_shared.h: main, posecov, models, symerr; lc_warp_grid.h: crop, maskcrop; lc_ray_length.h: vsd,
@@ -28,7 +29,8 @@ since that statement was written (bgstore, which includes lc_keyed_hash.h and lc
 augment's blend, pinned by tests/test_gpu_bgstore.py): "all of them" is `TARGETS + LATER_TARGETS`, in that order, and `build_later`
 builds the second tuple as `build` builds a member of the first.  `EXTRA_TARGETS` is where every library after that goes (shade, which
 includes no shared header and restates the rasteriser's snapped projection, pinned by tests/test_gpu_shade.py; obox, which includes no
-shared header either and whose fp32 rule is the one of models, pinned by tests/test_gpu_obox.py): "all of them" is
+shared header either and whose fp32 rule is the one of models, pinned by tests/test_gpu_obox.py; symfind, which includes none either and
+restates models' d2, pinned by tests/test_gpu_symfind.py): "all of them" is
 `TARGETS + LATER_TARGETS + EXTRA_TARGETS`, `build_later` builds the third tuple behind the second, and the next library joins the third
 tuple.  Every function takes the library it works on as a `Target`
 (default: the hot-path library)."""
@@ -107,7 +109,9 @@ LATER_TARGETS = (BGSTORE,)
 SHADE = _side("shade")  # the shading pass behind the rasteriser (lc_amd.shade); includes no shared header
 # every library added since, in build order behind LATER_TARGETS: the tuple the next library joins
 OBOX = _side("obox")  # the oriented model box search (lc_amd.obox, python -m lc_amd.prep_models --xform); includes no shared header
-EXTRA_TARGETS = (SHADE, OBOX)
+# the symmetry deviation of a model (lc_amd.symfind, python -m lc_amd.prep_models --check-symmetries / --symmetries); includes no shared header
+SYMFIND = _side("symfind")
+EXTRA_TARGETS = (SHADE, OBOX, SYMFIND)
 HASH_MARKER = MAIN.hash_marker
 
 
