@@ -18,6 +18,7 @@
     shade    lc_amd/_C/liblc_amd_shade.so    lc_amd/csrc/shade/       include/lc_amd_shade.h    the shading pass behind the rasteriser: uint8 frames of posed, vertex-coloured meshes
     obox     lc_amd/_C/liblc_amd_obox.so     lc_amd/csrc/obox/        include/lc_amd_obox.h     the oriented model box behind models_xform.json (an offline tool's kernels)
     symfind  lc_amd/_C/liblc_amd_symfind.so  lc_amd/csrc/symfind/     include/lc_amd_symfind.h  the symmetry deviation of a model: BOP's geometric rule, checked and searched (an offline tool's kernels)
+    texture  lc_amd/_C/liblc_amd_texture.so  lc_amd/csrc/texture/     include/lc_amd_texture.h  the textured shading pass: per-corner texture coordinates, a resident store of mip-mapped textures
 
 A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`): code that
 two libraries need exists once there (lc_shared.h: main, posecov, models, symerr; lc_warp_grid.h: crop, maskcrop; lc_ray_length.h: vsd,
@@ -30,7 +31,8 @@ augment's blend, pinned by tests/test_gpu_bgstore.py): "all of them" is `TARGETS
 builds the second tuple as `build` builds a member of the first.  `EXTRA_TARGETS` is where every library after that goes (shade, which
 includes no shared header and restates the rasteriser's snapped projection, pinned by tests/test_gpu_shade.py; obox, which includes no
 shared header either and whose fp32 rule is the one of models, pinned by tests/test_gpu_obox.py; symfind, which includes none either and
-restates models' d2, pinned by tests/test_gpu_symfind.py): "all of them" is
+restates models' d2, pinned by tests/test_gpu_symfind.py; texture, which includes none either and restates shade's pixel around a sampled
+albedo, pinned by tests/test_gpu_texshade.py): "all of them" is
 `TARGETS + LATER_TARGETS + EXTRA_TARGETS`, `build_later` builds the third tuple behind the second, and the next library joins the third
 tuple.  Every function takes the library it works on as a `Target`
 (default: the hot-path library)."""
@@ -111,7 +113,9 @@ SHADE = _side("shade")  # the shading pass behind the rasteriser (lc_amd.shade);
 OBOX = _side("obox")  # the oriented model box search (lc_amd.obox, python -m lc_amd.prep_models --xform); includes no shared header
 # the symmetry deviation of a model (lc_amd.symfind, python -m lc_amd.prep_models --check-symmetries / --symmetries); includes no shared header
 SYMFIND = _side("symfind")
-EXTRA_TARGETS = (SHADE, OBOX, SYMFIND)
+# the textured shading pass (lc_amd.texture); includes no shared header.  Not "texshade": tests/test_shade_host.py lets no other library's file carry "shade" in its name
+TEXTURE = _side("texture")
+EXTRA_TARGETS = (SHADE, OBOX, SYMFIND, TEXTURE)
 HASH_MARKER = MAIN.hash_marker
 
 
