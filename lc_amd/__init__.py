@@ -29,6 +29,8 @@ Call surface (mirrors the reference):
     lc_amd.backgrounds.BackgroundStore / switch_backgrounds   <- dataset.py:137-148,413-415 (_switch_bg with np.random.choice(self.bg_list): each row's background picked, cut and blended from a resident store; liblc_amd_bgstore.so)
     lc_amd.shade.shade / shade_scene / render_color / render_scene   <- tools/lib/meshrenderer/meshrenderer_phong.py:125-165 + dataset.py:413 (the `imgn` image: vertex colours under a Phong model behind the rasteriser's face map; liblc_amd_shade.so)
     lc_amd.texture.shade / shade_scene / render_color / render_scene / TextureStore / TexturedAppearance / read_ply_textured   <- tools/lib/pysixd/inout.py:505-617 (models with texture_u / texture_v or a face texcoord list and a texture image: the same frames with the albedo sampled from a resident store of mip-mapped textures at per-corner coordinates; liblc_amd_texture.so)
+    lc_amd.sampler.AnnotationTable / draw_rows / select_rows / take_rows   <- dataset.py:332-338 and the DataLoader's sampler and collate (a step's rows drawn from the seed word: every annotation once per epoch, spares at random; rows whose crop is too empty replaced by good spares in order; the batch gathered; liblc_amd_sampler.so)
+    lc_amd.trainset.TrainSet.step_inputs   the chain of lc_amd.train_inputs behind a resident annotation table: one seed word decides the step's batch, the cheap stages run on batch + spare rows, the expensive ones on exactly `batch`
     lc_amd.dropin                        run the reference's train.py / test.py on all of the above without editing them
 Native code: lc_amd/csrc/*.hip -> lc_amd/_C/liblc_amd.so (C ABI in include/lc_amd.h);
 lc_amd/csrc/optim/*.hip -> lc_amd/_C/liblc_amd_optim.so (include/lc_amd_optim.h);

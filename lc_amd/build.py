@@ -19,6 +19,7 @@
     obox     lc_amd/_C/liblc_amd_obox.so     lc_amd/csrc/obox/        include/lc_amd_obox.h     the oriented model box behind models_xform.json (an offline tool's kernels)
     symfind  lc_amd/_C/liblc_amd_symfind.so  lc_amd/csrc/symfind/     include/lc_amd_symfind.h  the symmetry deviation of a model: BOP's geometric rule, checked and searched (an offline tool's kernels)
     texture  lc_amd/_C/liblc_amd_texture.so  lc_amd/csrc/texture/     include/lc_amd_texture.h  the textured shading pass: per-corner texture coordinates, a resident store of mip-mapped textures
+    sampler  lc_amd/_C/liblc_amd_sampler.so  lc_amd/csrc/sampler/     include/lc_amd_sampler.h  the resident training set: a step's rows drawn from the seed word, the retry on valid_cnt, the gather
 
 A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`): code that
 two libraries need exists once there (lc_shared.h: main, posecov, models, symerr; lc_warp_grid.h: crop, maskcrop; lc_ray_length.h: vsd,
@@ -32,7 +33,8 @@ builds the second tuple as `build` builds a member of the first.  `EXTRA_TARGETS
 includes no shared header and restates the rasteriser's snapped projection, pinned by tests/test_gpu_shade.py; obox, which includes no
 shared header either and whose fp32 rule is the one of models, pinned by tests/test_gpu_obox.py; symfind, which includes none either and
 restates models' d2, pinned by tests/test_gpu_symfind.py; texture, which includes none either and restates shade's pixel around a sampled
-albedo, pinned by tests/test_gpu_texshade.py): "all of them" is
+albedo, pinned by tests/test_gpu_texshade.py; sampler, which includes lc_keyed_hash.h and lc_wave_int.h and restates nothing, pinned by
+tests/test_gpu_sampler.py): "all of them" is
 `TARGETS + LATER_TARGETS + EXTRA_TARGETS`, `build_later` builds the third tuple behind the second, and the next library joins the third
 tuple.  Every function takes the library it works on as a `Target`
 (default: the hot-path library)."""
@@ -74,8 +76,8 @@ SHARED = os.path.join(CSRC, "shared")
 SHARED_H = os.path.join(SHARED, "lc_shared.h")  # the fp64 cross-lane layer: the order-defining reductions of MAIN and POSECOV
 WARP_GRID_H = os.path.join(SHARED, "lc_warp_grid.h")  # the fixed-point warp coordinates and launch geometry of CROP and MASKCROP
 RAY_LENGTH_H = os.path.join(SHARED, "lc_ray_length.h")  # the ray length through a pixel and the phase-aligned group loads of VSD and GTINFO
-WAVE_INT_H = os.path.join(SHARED, "lc_wave_int.h")  # the integer wave butterflies of VSD, GTINFO and MASKCROP
-KEYED_HASH_H = os.path.join(SHARED, "lc_keyed_hash.h")  # the keyed integer hash of the device's random numbers of MASKCROP, AUGMENT and GEOMETRY
+WAVE_INT_H = os.path.join(SHARED, "lc_wave_int.h")  # the integer wave butterflies of VSD, GTINFO, MASKCROP and SAMPLER
+KEYED_HASH_H = os.path.join(SHARED, "lc_keyed_hash.h")  # the keyed integer hash of the device's random numbers of MASKCROP, AUGMENT, GEOMETRY, BGSTORE and SAMPLER
 BYTE_FINISH_H = os.path.join(SHARED, "lc_byte_finish.h")  # the finished output value of an image byte of CROP and AUGMENT
 
 
@@ -115,7 +117,9 @@ OBOX = _side("obox")  # the oriented model box search (lc_amd.obox, python -m lc
 SYMFIND = _side("symfind")
 # the textured shading pass (lc_amd.texture); includes no shared header.  Not "texshade": tests/test_shade_host.py lets no other library's file carry "shade" in its name
 TEXTURE = _side("texture")
-EXTRA_TARGETS = (SHADE, OBOX, SYMFIND, TEXTURE)
+# the training loader's resident annotations (lc_amd.sampler, lc_amd.trainset): hashes as MASKCROP does, sums a wavefront as VSD does
+SAMPLER = _side("sampler", (KEYED_HASH_H, WAVE_INT_H))
+EXTRA_TARGETS = (SHADE, OBOX, SYMFIND, TEXTURE, SAMPLER)
 HASH_MARKER = MAIN.hash_marker
 
 
