@@ -20,6 +20,7 @@
     symfind  lc_amd/_C/liblc_amd_symfind.so  lc_amd/csrc/symfind/     include/lc_amd_symfind.h  the symmetry deviation of a model: BOP's geometric rule, checked and searched (an offline tool's kernels)
     texture  lc_amd/_C/liblc_amd_texture.so  lc_amd/csrc/texture/     include/lc_amd_texture.h  the textured shading pass: per-corner texture coordinates, a resident store of mip-mapped textures
     sampler  lc_amd/_C/liblc_amd_sampler.so  lc_amd/csrc/sampler/     include/lc_amd_sampler.h  the resident training set: a step's rows drawn from the seed word, the retry on valid_cnt, the gather
+    posedraw lc_amd/_C/liblc_amd_posedraw.so lc_amd/csrc/posedraw/    include/lc_amd_posedraw.h the synthetic scenes' object poses drawn from the seed word: uniform rotations, sphere-separated positions
 
 A library's source hash covers its directory, its header and the headers of lc_amd/csrc/shared/ it declares (`Target.shared`): code that
 two libraries need exists once there (lc_shared.h: main, posecov, models, symerr; lc_warp_grid.h: crop, maskcrop; lc_ray_length.h: vsd,
@@ -34,7 +35,8 @@ includes no shared header and restates the rasteriser's snapped projection, pinn
 shared header either and whose fp32 rule is the one of models, pinned by tests/test_gpu_obox.py; symfind, which includes none either and
 restates models' d2, pinned by tests/test_gpu_symfind.py; texture, which includes none either and restates shade's pixel around a sampled
 albedo, pinned by tests/test_gpu_texshade.py; sampler, which includes lc_keyed_hash.h and lc_wave_int.h and restates nothing, pinned by
-tests/test_gpu_sampler.py): "all of them" is
+tests/test_gpu_sampler.py; posedraw, which includes lc_keyed_hash.h and restates geometry's cosine and sine polynomial, pinned by
+tests/test_gpu_posedraw.py): "all of them" is
 `TARGETS + LATER_TARGETS + EXTRA_TARGETS`, `build_later` builds the third tuple behind the second, and the next library joins the third
 tuple.  Every function takes the library it works on as a `Target`
 (default: the hot-path library)."""
@@ -77,7 +79,7 @@ SHARED_H = os.path.join(SHARED, "lc_shared.h")  # the fp64 cross-lane layer: the
 WARP_GRID_H = os.path.join(SHARED, "lc_warp_grid.h")  # the fixed-point warp coordinates and launch geometry of CROP and MASKCROP
 RAY_LENGTH_H = os.path.join(SHARED, "lc_ray_length.h")  # the ray length through a pixel and the phase-aligned group loads of VSD and GTINFO
 WAVE_INT_H = os.path.join(SHARED, "lc_wave_int.h")  # the integer wave butterflies of VSD, GTINFO, MASKCROP and SAMPLER
-KEYED_HASH_H = os.path.join(SHARED, "lc_keyed_hash.h")  # the keyed integer hash of the device's random numbers of MASKCROP, AUGMENT, GEOMETRY, BGSTORE and SAMPLER
+KEYED_HASH_H = os.path.join(SHARED, "lc_keyed_hash.h")  # the keyed integer hash of the device's random numbers of MASKCROP, AUGMENT, GEOMETRY, BGSTORE, SAMPLER and POSEDRAW
 BYTE_FINISH_H = os.path.join(SHARED, "lc_byte_finish.h")  # the finished output value of an image byte of CROP and AUGMENT
 
 
@@ -119,7 +121,9 @@ SYMFIND = _side("symfind")
 TEXTURE = _side("texture")
 # the training loader's resident annotations (lc_amd.sampler, lc_amd.trainset): hashes as MASKCROP does, sums a wavefront as VSD does
 SAMPLER = _side("sampler", (KEYED_HASH_H, WAVE_INT_H))
-EXTRA_TARGETS = (SHADE, OBOX, SYMFIND, TEXTURE, SAMPLER)
+# the synthetic scenes' object poses drawn on the device from the seed word (lc_amd.posedraw, lc_amd.synthscene); hashes as MASKCROP does
+POSEDRAW = _side("posedraw", (KEYED_HASH_H,))
+EXTRA_TARGETS = (SHADE, OBOX, SYMFIND, TEXTURE, SAMPLER, POSEDRAW)
 HASH_MARKER = MAIN.hash_marker
 
 
